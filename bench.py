@@ -19,8 +19,18 @@ The product's N=1 exchange runs pack+unpack as ONE launch (k_self: each lane pac
 bytes and writes the halos from the same registers, so the buffer is never read back): it moves
 3 * n * 8 bytes and is reported as "fused_self" with exactly those bytes, not as the headline.
 
-Before timing, one full exchange (pack -> RCCL send/recv over xGMI for N>1 -> unpack) is run and
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: it sets up (one full
+exchange allocates the plan's buffers), resets the halos and send buffers, warms up, times the K
+steps, and prints the line (metric, value, ms_per_step, config). `--dump-outputs DIR` also writes
+what the last timed step computed (the send buffers and the field's halo cells, float64 .npy):
+the inputs are synthetic and identical from run to run, so two builds can be compared array by
+array. Everything below is run only with `--full`.
+
+With --full, before timing, one full exchange (pack -> RCCL send/recv over xGMI for N>1 ->
+unpack) is run and
 every cell of every rank's (N+2H)^3 box is verified on the GPU against the wrapped global index.
+After the timed region the timed graphs themselves are verified (`verified`) and the per-kernel
+roofline figures are taken.
 Extra fields: cold-cache launch times (default; --no-cold for profiler runs), the full exchange
 time incl. RCCL (one group, and per-peer pipelined), the host-staged rate (pack + D2H + H2D +
 unpack through pinned memory), and on rank 0 at N=1 the oracle's single-thread CPU pack+unpack
@@ -50,6 +60,15 @@ def parse():
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--N", type=int, default=512)
     p.add_argument("--halo", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run everything else the bench measures or "
+                        "checks: the verifications, the per-kernel roofline figures, the cold-"
+                        "cache legs, the other configs and halo widths, the full exchanges and "
+                        "the CPU baselines (the --no-* options below trim that part)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what their last step computed as "
+                        "DIR/<name>.npy (float64): the send buffers the pack filled and the "
+                        "field's halo cells the unpack wrote")
     p.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph")
     p.add_argument("--steps-per-graph", type=int, default=0,
                    help="steps captured per hipGraph (the K timed steps replay K/G graphs); "
@@ -264,6 +283,40 @@ def verify_replay(torch, dev, replay, clear, count_bad, send, recv, deliver=None
         replay()
     torch.cuda.synchronize(dev)
     return count_bad()
+
+
+DUMP_BYTES_PER_ARRAY = 30_000_000  # two arrays per rank: 60 MB in all at most
+DUMP_SEED = 20260715
+
+
+def _dump_sample(a):
+    """a, or (above DUMP_BYTES_PER_ARRAY) its elements at a fixed, seeded, sorted set of indices."""
+    import numpy as np
+    cap = DUMP_BYTES_PER_ARRAY // a.itemsize
+    if a.size <= cap:
+        return a
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=cap, replace=False))
+    return a[idx]
+
+
+def dump_outputs(path, torch, base, N, Hw, plan, send, rank, world):
+    """--dump-outputs: what the last timed step left behind, as float64 .npy files in `path`:
+      send_buffers  the bytes the pack launch wrote, every send buffer in plan order;
+      field_halo    the halo cells the unpack launch wrote: the field's six halo slabs (z low, z
+                    high, then y, then x of the remaining box) in memory order.
+    The owned cells are the inputs and are not written. Each array is whole up to
+    DUMP_BYTES_PER_ARRAY, above that a fixed seeded sample of it. At N>1 every rank writes its
+    own files (<name>.rank<r>.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    o = slice(Hw, Hw + N)
+    slabs = [base[:Hw], base[Hw + N:], base[o, :Hw], base[o, Hw + N:], base[o, o, :Hw],
+             base[o, o, Hw + N:]]
+    halo = torch.cat([x.reshape(-1) for x in slabs]).cpu().numpy()
+    bufs = torch.cat([send[i][:x["size"]] for i, x in enumerate(plan.send)]).cpu().numpy()
+    tag = "" if world == 1 else f".rank{rank}"
+    for name, a in (("send_buffers", bufs.view(np.float64)), ("field_halo", halo)):
+        np.save(os.path.join(path, f"{name}{tag}.npy"), _dump_sample(a))
 
 
 def bulk_child(args):
@@ -655,9 +708,10 @@ def main():
             ar[0].view(1, 1, N) + G[0] * (ar[1].view(1, N, 1) + G[1] * ar[2].view(N, 1, 1)))
 
     # ---- verified full exchange (pack -> RCCL -> unpack) --------------------------------------
+    # (a plain run needs the exchange only as setup: it allocates the plan's buffers)
     with guard.stage("verified_exchange", args.exchange_timeout):
         co.exchange(bis).wait()
-        verified = verify() == 0
+        verified = verify() == 0 if args.full else None
     headline = guard.stage("headline", args.headline_timeout)
     headline.__enter__()
 
@@ -696,6 +750,12 @@ def main():
     K, W = args.steps, args.warmup
     spg = args.steps_per_graph or min(K, 1000)  # steps per hipGraph
     runner = Runner(torch, dev, stream, step, spg, eager=args.no_graph)
+    # halos back to -1 and every send-buffer byte to 0xFF (an fp64 NaN) before the first step, so
+    # that what --dump-outputs writes after the timed steps was computed by those steps (the peer
+    # messages of the setup exchange stay in the receive buffers, N>1)
+    clear_halos()
+    for t in send:
+        t.fill_(255)
     runner.prepare(W)
     runner.prepare(K)
     runner.run(W)
@@ -727,6 +787,42 @@ def main():
     dev_time = {}
     T = timed(lambda: runner.run(K), 1, events=True, box=dev_time)
     dev_step = dev_time["s"] / K  # device time per step over the timed region (HIP events)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, base, N, Hw, plan, send, rank, world)
+    value = world * step_bytes * K / T / 1e9
+    out = {
+        "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": world,
+        "steps": K, "warmup": W, "ms_per_step": round(T / K * 1e3, 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic (owned cell = global linear index; halos -1 before every verification)",
+        "config": {
+            "workload": f"{N}^3 fp64 structured 3D halo={Hw}, 26-neighbour periodic, "
+                        f"device-resident pack+unpack, decomposition {list(parts)}",
+            "N": N, "halo": Hw, "fields": 1, "decomposition": list(parts),
+            "launch": ("eager" if args.no_graph else
+                       f"hipGraphs of {spg} steps, instantiated before the timed region") +
+                      ", pack launch + unpack launch per step",
+            "bytes_per_step_per_gpu": step_bytes,
+            "parallelism": f"{world} rank(s), one domain per GPU",
+            "world_size": world, "backend": backend,
+        },
+        "full": args.full,
+    }
+    if args.dump_outputs:
+        out["outputs_dumped"] = args.dump_outputs
+    if not args.full:
+        # a plain run ends here: the headline alone, nothing verified or measured beside it
+        if args.rehearse:
+            out["rehearsal"] = ("all ranks on cuda:0, gloo + host-staged transport: code-path "
+                                "check, not the metric")
+        headline.__exit__(None, None, None)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+            _LINE["printed"] = True
+        if distributed:
+            barrier()
+            dist.destroy_process_group()
+        return
     # `verified` refers to the kernels just timed: halos back to -1, every buffer byte to 0xFF,
     # the timed graph replayed once (N>1: then the peer messages' transport and an unpack), every
     # cell checked. The first exchange above (at N=1 the fused k_self) is `verified_fused`.
@@ -749,23 +845,7 @@ def main():
     with guard.stage("verify_timed", args.exchange_timeout):
         verified = verify_replay(torch, dev, lambda: runner.run(K), clear_halos, verify,
                                  send, recv, transport if t_recvs else None) == 0
-    value = world * step_bytes * K / T / 1e9
-    out = {
-        "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": world,
-        "steps": K, "warmup": W, "ms_per_step": round(T / K * 1e3, 5),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic (owned cell = global linear index; halos -1 before every verification)",
-        "config": {
-            "workload": f"{N}^3 fp64 structured 3D halo={Hw}, 26-neighbour periodic, "
-                        f"device-resident pack+unpack, decomposition {list(parts)}",
-            "N": N, "halo": Hw, "fields": 1, "decomposition": list(parts),
-            "launch": ("eager" if args.no_graph else
-                       f"hipGraphs of {spg} steps, instantiated before the timed region") +
-                      ", pack launch + unpack launch per step",
-            "bytes_per_step_per_gpu": step_bytes,
-            "parallelism": f"{world} rank(s), one domain per GPU",
-            "world_size": world, "backend": backend,
-        },
+    out.update({
         "verified": verified,
         "verified_what": "after the timed region, on halos reset to -1 and every buffer byte "
                          "set to 0xFF: the timed hipGraphs (k_copy pack + k_copy unpack, K "
@@ -778,7 +858,7 @@ def main():
         "verified_fused_what": ("the first exchange: co.exchange() = the fused k_self launch"
                                 if world == 1 and co.fuse_self and co.all_self(plan) else
                                 "the first exchange: co.exchange() = pack, transport, unpack"),
-    }
+    })
     if args.rehearse:
         out["rehearsal"] = ("all ranks on cuda:0, gloo + host-staged transport: code-path check, "
                             "not the metric")

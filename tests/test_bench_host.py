@@ -266,6 +266,27 @@ def test_bulk_only_mode_reports_failed_children():
     assert o["mode"] == "bulk-only" and o["n_procs"] == 2 and "error" in o
 
 
+def test_full_and_dump_outputs_options(monkeypatch):
+    """--full is off by default and --dump-outputs takes a directory; the dumped arrays stay
+    whole up to the per-array cap (two arrays: under 64 MB in all), above it the same seeded,
+    ordered sample every time."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    assert 2 * bench.DUMP_BYTES_PER_ARRAY <= 64_000_000
+    cap = bench.DUMP_BYTES_PER_ARRAY // 8
+    small = np.arange(cap, dtype=np.float64)
+    assert bench._dump_sample(small) is small
+    big = np.arange(cap + 1000, dtype=np.float64)
+    s1, s2 = bench._dump_sample(big), bench._dump_sample(big)
+    assert s1.shape == (cap,) and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+
+
 def test_config5_patterns_small_and_cpu_baseline_keys():
     """config5_patterns (8 ranks' product make_pattern as threads) at a small size: every peer's
     send list to rank 0 carries rank 0's receive gids; cpu_baseline_config5's keys, and its

@@ -1,4 +1,5 @@
-"""bench.py's contract on the GPU box, at a small size: one JSON line with the metric's fields, the
+"""bench.py's contract on a GPU, at a small size: a plain run's line and its dumped outputs;
+with --full one JSON line with the metric's fields, the
 roofline / cpu-free extras, a verified exchange; and the N>1 path through bench.py's own rank
 spawning (`--gpus 2 --rehearse`: both ranks on the one GPU, gloo + host staging, the pipelined
 exchange included). Each run is a child process bounded by a timeout."""
@@ -29,8 +30,42 @@ def _bench(*args, timeout=150):
     return json.loads(lines[0])
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full: the line's headline fields, --steps timed steps, none of the extras; and
+    --dump-outputs writes what the last timed step computed (halos and send buffers are reset
+    before the first step): every halo cell holds its wrapped global linear index, and the send
+    buffers hold the same values (each halo cell is one packed cell)."""
+    import numpy as np
+    N, H = 64, 2
+    E, n = N + 2 * H, (N + 2 * H) ** 3 - N ** 3
+    d = _bench("--gpus", "1", "--N", str(N), "--steps", "12", "--warmup", "3",
+               "--dump-outputs", str(tmp_path / "out"))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+              "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    assert d["full"] is False and d["steps"] == 12 and d["warmup"] == 3 and d["n_gpus"] == 1
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - 4 * n * 8 / (d["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * d["value"]
+    for k in ("roofline", "verified", "fused_self", "halo_widths", "extra_configs",
+              "cpu_baseline", "host_staged", "bulk", "exchange_ms_per_step"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path / "out")) == ["field_halo.npy", "send_buffers.npy"]
+    halo = np.load(tmp_path / "out" / "field_halo.npy")
+    bufs = np.load(tmp_path / "out" / "send_buffers.npy")
+    assert halo.dtype == np.float64 and bufs.dtype == np.float64
+    assert halo.shape == (n,) and bufs.shape == (n,)
+    w = (np.arange(E) - H) % N
+    want = (w[None, None, :] + N * (w[None, :, None] + N * w[:, None, None])).astype(np.float64)
+    o = slice(H, H + N)
+    slabs = [want[:H], want[H + N:], want[o, :H], want[o, H + N:], want[o, o, :H],
+             want[o, o, H + N:]]
+    assert np.array_equal(halo, np.concatenate([s.reshape(-1) for s in slabs]))
+    assert np.array_equal(np.sort(bufs), np.sort(halo))
+
+
 def test_bench_line_n1_small():
-    d = _bench("--N", "64", "--steps", "12", "--warmup", "3", "--no-cpu-baseline")
+    d = _bench("--N", "64", "--steps", "12", "--warmup", "3", "--no-cpu-baseline", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
               "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
@@ -71,7 +106,7 @@ def test_bench_line_n1_small():
 
 def test_bench_spawns_two_ranks_rehearsal():
     d = _bench("--gpus", "2", "--rehearse", "--N", "64", "--steps", "10", "--warmup", "2",
-               "--no-cold", timeout=240)
+               "--no-cold", "--full", timeout=240)
     assert d["n_gpus"] == 2 and d["verified"] is True and d["verified_fused"] is True
     assert "transported into the receive buffers" in d["verified_what"]
     for h, x in d["halo_widths"].items():

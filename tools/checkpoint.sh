@@ -10,7 +10,7 @@
 #   smoke            __graft_entry__.smoke()
 #   bench            bench.py at the driver's settings (--steps 20 --warmup 5)
 #   bench=<args>     bench.py <args>  (e.g. "bench=--no-cold --no-extras")
-#   rehearse=<n>     bench.py --gpus n --rehearse (n=2/4 through bench.py's own spawning, n=8
+#   rehearse=<n>     bench.py --full --gpus n --rehearse (n=2/4 through bench.py's own spawning, n=8
 #                    through torch.distributed.run as the driver launches it)
 #   bulkn=<n>        bench.py --bulk-only n: the N>1 isolated zero-copy leg alone (n children on
 #                    the one GPU: puts + direct, verified)
@@ -41,10 +41,10 @@ for s in "$@"; do
     rehearse)
       if [ "$arg" = 8 ]; then
         timeout -k 10 $LIM python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-          --master-addr 127.0.0.1 --master-port 29508 bench.py --gpus 8 --rehearse \
+          --master-addr 127.0.0.1 --master-port 29508 bench.py --full --gpus 8 --rehearse \
           --steps 50 --warmup 5 > $O/$i-rehearse$arg.json 2> $log
       else
-        timeout -k 10 $LIM python bench.py --gpus $arg --rehearse --steps 50 --warmup 5 \
+        timeout -k 10 $LIM python bench.py --full --gpus $arg --rehearse --steps 50 --warmup 5 \
           > $O/$i-rehearse$arg.json 2> $log
       fi ;;
     bulkn) timeout -k 10 $LIM python bench.py --bulk-only $arg --steps 20 \

@@ -9,10 +9,10 @@ set -e
 OUT=${1:-gpurun_out/rehearse}
 mkdir -p $OUT
 for n in 2 4; do
-  timeout -k 10 300 python bench.py --gpus $n --rehearse --steps 50 --warmup 5 \
+  timeout -k 10 300 python bench.py --full --gpus $n --rehearse --steps 50 --warmup 5 \
     > $OUT/n$n.json 2> $OUT/n$n.err
 done
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-  --master-addr 127.0.0.1 --master-port 29508 bench.py --gpus 8 --rehearse \
+  --master-addr 127.0.0.1 --master-port 29508 bench.py --full --gpus 8 --rehearse \
   --steps 50 --warmup 5 > $OUT/n8.json 2> $OUT/n8.err
 echo done > $OUT/DONE

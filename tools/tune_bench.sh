@@ -7,6 +7,6 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/tune_bench.jsonl
 : > $OUT
 for t in "$@"; do
-  line=$(timeout -k 10 120 python $R/bench.py --no-cpu-baseline --no-extras --tune "$t" | tail -1)
+  line=$(timeout -k 10 120 python $R/bench.py --full --no-cpu-baseline --no-extras --tune "$t" | tail -1)
   echo "{\"tune\": \"$t\", \"bench\": $line}" >> $OUT
 done
