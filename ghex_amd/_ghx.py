@@ -30,6 +30,14 @@ class PackEntry(ctypes.Structure):
                 ("buffer_offset", c_u64), ("boxes", ctypes.POINTER(Box)), ("n_boxes", c_i32)]
 
 
+class SegmentInfo(ctypes.Structure):
+    _fields_ = [("field_off", c_i64), ("buf_off", c_u64), ("stride", c_i64 * 4),
+                ("ext", ctypes.c_uint32 * 4), ("row_bytes", ctypes.c_uint32),
+                ("bytes", ctypes.c_uint32), ("tile_bytes", ctypes.c_uint32),
+                ("field_slot", c_i32), ("buffer_slot", c_i32), ("n_outer", c_i32),
+                ("wlog2", c_i32), ("amode", c_i32), ("pipe", c_i32)]
+
+
 class UDataDesc(ctypes.Structure):
     _fields_ = [("elem_size", c_i32), ("levels", c_i32), ("levels_first", c_i32),
                 ("index_stride", c_i64), ("level_stride", c_i64)]
@@ -61,6 +69,7 @@ _SIGS = {
     "ghx_plan_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_plan_destroy": (c_i32, [c_vp]),
     "ghx_plan_info": (c_i32, [c_vp, P(c_u64), P(c_i32), P(c_i32)]),
+    "ghx_plan_segment": (c_i32, [c_vp, c_i32, P(SegmentInfo)]),
     "ghx_structured_pack": (c_i32, [P(FieldDesc), c_vp, c_vp, P(Box), c_i32, c_vp]),
     "ghx_structured_unpack": (c_i32, [P(FieldDesc), c_vp, c_vp, P(Box), c_i32, c_vp]),
     "ghx_uplan_create": (c_i32, [P(UPackEntry), c_i32, c_i32, P(c_vp)]),

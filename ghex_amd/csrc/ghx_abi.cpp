@@ -645,6 +645,46 @@ int ghx_plan_info(const ghx_plan* plan, uint64_t* bytes, int32_t* n_segments, in
     });
 }
 
+int ghx_plan_segment(const ghx_plan* plan, int32_t k, ghx_segment_info* out)
+{
+    return guarded([&] {
+        check_ptr(plan, "plan");
+        check_ptr(out, "out");
+        if (k < 0 || k >= plan->n_segments) throw invalid("segment index out of range");
+        // the host copies of the launch groups, in plan order (partition_slots keeps it)
+        const std::vector<seg_s>* segs = &plan->host_segs;
+        const std::vector<int32_t>*fm = &plan->fmap, *bm = &plan->bmap;
+        size_t i = size_t(k);
+        for (size_t g = 0; i >= segs->size(); ++g)
+        {
+            i -= segs->size();
+            if (g >= plan->more.size()) throw invalid("segment index out of range");
+            segs = &plan->more[g]->host_segs;
+            fm = &plan->more[g]->fmap;
+            bm = &plan->more[g]->bmap;
+        }
+        const seg_s& s = (*segs)[i];
+        *out = ghx_segment_info{};
+        out->field_off = s.field_off;
+        out->buf_off = s.buf_off;
+        for (int d = 0; d < 4; ++d)
+        {
+            out->stride[d] = s.stride[d];
+            out->ext[d] = s.ext[d];
+        }
+        out->row_bytes = s.row_bytes;
+        out->bytes = s.bytes;
+        out->tile_bytes = s.tile_bytes;
+        out->field_slot = fm->empty() ? int32_t(s.field_slot) : (*fm)[s.field_slot];
+        out->buffer_slot = bm->empty() ? int32_t(s.buf_slot) : (*bm)[s.buf_slot];
+        out->n_outer = s.n_outer;
+        out->wlog2 = s.wlog2;
+        out->amode = s.amode;
+        out->pipe = s.pipe;
+        return GHX_OK;
+    });
+}
+
 int ghx_structured_pack(const ghx_field_desc* field, const void* field_data, void* buffer,
                         const ghx_box* boxes, int32_t n_boxes, ghx_stream stream)
 {

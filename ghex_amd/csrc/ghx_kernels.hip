@@ -615,7 +615,7 @@ __device__ __forceinline__ void copy_any(const Seg& s, char* field, char* buf, u
         }
         else if (s.amode == 2 && w == 4)
         {
-            copy_tile<PACK, 16, Seg, 2>(s, field, buf, start, end);
+            copy_tile<PACK, 16, Seg, 2, UU>(s, field, buf, start, end);
             return;
         }
     }

@@ -149,6 +149,34 @@ int ghx_plan_destroy(ghx_plan* plan);
  * space), number of workgroup tiles, and the largest byte offset+size touched per buffer slot. */
 int ghx_plan_info(const ghx_plan* plan, uint64_t* bytes, int32_t* n_segments, int32_t* n_tiles);
 
+/* What the planner decided for one segment (introspection only; no reference counterpart): the
+ * host copy of segment k of a plan, k in [0, n_segments) of ghx_plan_info — the segments of all
+ * launch groups in plan order (entries, their boxes, the pieces of a box split below 2^31 bytes).
+ * A segment is `bytes / row_bytes` rows of `row_bytes` contiguous field bytes; row r sits at
+ * field_off + sum_k c_k * stride[k] with r = c_0 + ext[0] * (c_1 + ext[1] * (c_2 + ext[2] * c_3))
+ * and at buf_off + r * row_bytes in its buffer. wlog2: log2 of the widest vector the planner
+ * allows (the launch narrows it by the pointers' alignment); amode: the field-offset arithmetic
+ * the kernels take for it, 0 = general (int64), 1 / 2 = the short form ("fast_addr") with one /
+ * two divisions; pipe: unpack tiles software-pipelined. Slots are the caller's. Works on plans
+ * created without a device. k out of range: GHX_ERR_INVALID. */
+typedef struct ghx_segment_info
+{
+    int64_t field_off;
+    uint64_t buf_off;
+    int64_t stride[4];
+    uint32_t ext[4];
+    uint32_t row_bytes;
+    uint32_t bytes;
+    uint32_t tile_bytes;
+    int32_t field_slot;
+    int32_t buffer_slot;
+    int32_t n_outer;
+    int32_t wlog2;
+    int32_t amode;
+    int32_t pipe;
+} ghx_segment_info;
+int ghx_plan_segment(const ghx_plan* plan, int32_t k, ghx_segment_info* out);
+
 /* The reference's field.pack(T* buffer, const IndexContainer& c, void* arg)
  * (include/ghex/structured/regular/field_descriptor.hpp:72-83) for ONE field: iteration spaces
  * back to back from `buffer`. Convenience form of plan_create+execute (the descriptor upload is
