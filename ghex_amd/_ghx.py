@@ -52,6 +52,16 @@ class RegularDomain(ctypes.Structure):
     _fields_ = [("id", c_i32), ("rank", c_i32), ("first", c_i32 * 3), ("last", c_i32 * 3)]
 
 
+class CsDomain(ctypes.Structure):
+    _fields_ = [("rank", c_i32), ("tile", c_i32), ("x_first", c_i32), ("x_last", c_i32),
+                ("y_first", c_i32), ("y_last", c_i32)]
+
+
+class CsItem(ctypes.Structure):
+    _fields_ = [("tile", c_i32), ("first_x", c_i32), ("first_y", c_i32), ("edge_size", c_i32),
+                ("is_vector", c_i32), ("value_kind", c_i32)]
+
+
 class ExchangeItem(ctypes.Structure):
     _fields_ = [("pattern", c_vp), ("local_index", c_i32), ("kind", c_i32), ("field", FieldDesc),
                 ("udata", UDataDesc), ("align", c_i32), ("tag_offset", c_i32)]
@@ -82,6 +92,15 @@ _SIGS = {
                                            P(c_i32), P(c_i32), c_i32, P(c_vp)]),
     "ghx_staged_pattern_create": (c_i32, [c_i32, P(RegularDomain), c_i32, P(c_i32), P(c_i32),
                                           P(c_i32), P(c_i32), P(c_i32), c_i32, P(c_vp)]),
+    "ghx_cs_halo_boxes": (c_i32, [c_i32, c_i32, P(CsDomain), P(c_i32), P(Box), P(Box), P(c_i32),
+                                  c_i32, P(c_i32)]),
+    "ghx_cs_pattern_create": (c_i32, [c_i32, c_i32, P(CsDomain), c_i32, P(c_i32), c_i32,
+                                      P(c_vp)]),
+    "ghx_pattern_key_tiles": (c_i32, [c_vp, c_i32, c_i32, c_i32, P(c_i32), c_i32]),
+    "ghx_cs_exchange_create": (c_i32, [P(ExchangeItem), P(CsItem), c_i32, P(c_vp)]),
+    "ghx_cs_plan_info": (c_i32, [c_vp, P(c_i32), P(c_u64), P(c_i32), P(c_i32)]),
+    "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
+                              c_i32, c_vp]),
     "ghx_udomain_create": (c_i32, [c_i32, P(c_i64), c_i64, P(c_i64), c_i64, P(c_vp)]),
     "ghx_udomain_destroy": (c_i32, [c_vp]),
     "ghx_udomain_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i64)]),

@@ -255,6 +255,10 @@ class BulkCommunicationObject:
             raise RuntimeError("error: this bulk communication object has been initialized already")
         if bi.field.kind != 0:
             raise TypeError("bulk (zero-copy) exchange is implemented for structured fields")
+        if getattr(bi.field, "cs_item", None) is not None:
+            # a put copies field to field in the sender's orientation: it cannot rotate a halo
+            # that crosses a cube edge (ghx_put_create knows fields and boxes only)
+            raise ValueError("bulk (zero-copy) exchange does not take cubed-sphere fields")
         self._bis.append(bi)
 
     def add_fields(self, *bis):

@@ -54,10 +54,14 @@ from . import _ghx
 
 
 class _ExchangePlan:
-    def __init__(self, items: List[_ghx.ExchangeItem]):
+    def __init__(self, items: List[_ghx.ExchangeItem], cs_items=None):
         arr = (_ghx.ExchangeItem * len(items))(*items)
         h = ctypes.c_void_p()
-        _ghx.call("ghx_exchange_create", arr, len(items), ctypes.byref(h))
+        if cs_items is None:
+            _ghx.call("ghx_exchange_create", arr, len(items), ctypes.byref(h))
+        else:  # cubed-sphere fields (ghex_amd.structured.cubed_sphere): the rotating unpack
+            cs = (_ghx.CsItem * len(cs_items))(*cs_items)
+            _ghx.call("ghx_cs_exchange_create", arr, cs, len(items), ctypes.byref(h))
         self.h = h
         self.send = self._buffers(0)
         self.recv = self._buffers(1)
@@ -313,13 +317,28 @@ class CommunicationObject:
         k = []
         for bi in bis:
             f = bi.field
-            k.append((id(bi.pattern_container), bi.local_index, f.kind, bytes(f.desc), f.align))
+            cs = getattr(f, "cs_item", None)
+            k.append((id(bi.pattern_container), bi.local_index, f.kind, bytes(f.desc), f.align,
+                      None if cs is None else bytes(cs)))
         return tuple(k)
 
     def plan(self, bis):
         key = self._key(bis)
         p = self._plans.get(key)
         if p is None:
+            # cubed-sphere fields (their unpack rotates halos that cross a cube edge) take
+            # ghx_cs_exchange_create; the per-peer pipeline and the direct exchange unpack
+            # buffer by buffer / from double-buffered copies, which do not rotate
+            cs = [getattr(bi.field, "cs_item", None) for bi in bis]
+            if any(c is not None for c in cs):
+                if not all(c is not None for c in cs):
+                    raise ValueError("an exchange takes cubed-sphere fields or other fields, "
+                                     "not both")
+                if self.pipelined or self.direct:
+                    raise ValueError("cubed-sphere fields are exchanged by the plain "
+                                     "communication object (no pipelined=True, no direct=True)")
+            else:
+                cs = None
             # tag offsets per distinct pattern container (prepare_exchange_buffers :540-549)
             offsets, acc = {}, 0
             for bi in bis:
@@ -340,7 +359,7 @@ class CommunicationObject:
                 it.align = bi.field.align
                 it.tag_offset = offsets[id(bi.pattern_container)]
                 items.append(it)
-            p = _ExchangePlan(items)
+            p = _ExchangePlan(items, cs)
             self._plans[key] = (p, [bi.pattern_container for bi in bis])
         else:
             p = p[0]

@@ -13,6 +13,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "ghx_cubed_sphere.hpp"
 #include "ghx_exchange.hpp"
 #include "ghx_guard.hpp"
 #include "ghx_pattern.hpp"
@@ -195,6 +196,63 @@ int run_structured(const ghx_field_desc& f, const ghx_box* boxes, int n, int dir
     return rc;
 }
 
+// ghx_cs_unpack's cached plan: the ordinary and the transformed part of one field's spaces
+struct cs_field_plan
+{
+    std::unique_ptr<splan> s;
+    std::unique_ptr<xplan> x;
+};
+
+plan_lru<cs_field_plan>& cs_cache()
+{
+    static plan_lru<cs_field_plan> c;
+    return c;
+}
+
+int run_cs_unpack(const ghx_field_desc& f, const ghx_cs_item& cs, const ghx_box* local,
+                  const ghx_box* global, const int32_t* tiles, int n, void* field, void* buffer,
+                  void* stream)
+{
+    std::string key(reinterpret_cast<const char*>(&f), sizeof(f));
+    key.append(reinterpret_cast<const char*>(&cs), sizeof(cs));
+    key.append(reinterpret_cast<const char*>(local), sizeof(ghx_box) * size_t(n));
+    key.append(reinterpret_cast<const char*>(global), sizeof(ghx_box) * size_t(n));
+    key.append(reinterpret_cast<const char*>(tiles), sizeof(int32_t) * size_t(n));
+    auto c = cs_cache().get(
+        key, [](const cached_plan<cs_field_plan>&) { return true; },
+        [&] {
+            cs_recv_plan rp;
+            uint64_t off = 0;
+            for (int b = 0; b < n; ++b)
+            {
+                is_pair sp{};
+                for (int k = 0; k < 3; ++k)
+                {
+                    sp.lf[k] = local[b].first[k];
+                    sp.ll[k] = local[b].last[k];
+                    sp.gf[k] = global[b].first[k];
+                    sp.gl[k] = global[b].last[k];
+                }
+                uint64_t nb = 0;
+                cs_plan_space(rp, f, cs, sp, tiles[b], 0, 0, off, &nb);
+                off += nb;
+            }
+            auto p = std::make_shared<cached_plan<cs_field_plan>>();
+            p->plan = std::make_unique<cs_field_plan>();
+            if (!rp.segs.empty())
+                p->plan->s = std::make_unique<splan>(std::move(rp.segs), rp.gf, rp.gb, rp.sbytes, 1);
+            if (!rp.xs.empty()) p->plan->x = std::make_unique<xplan>(std::move(rp.xs));
+            return p;
+        });
+    void* fp[1] = {field};
+    void* bp[1] = {buffer};
+    int rc = GHX_OK;
+    if (c->plan->s) rc = c->plan->s->execute(fp, 1, bp, 1, stream);
+    if (rc == GHX_OK && c->plan->x) rc = c->plan->x->execute(fp, 1, bp, 1, stream);
+    cs_cache().used(*c, stream);
+    return rc;
+}
+
 int run_unstructured(const ghx_udata_desc& d, const void* lids, int32_t lid_bytes, int64_t n,
                      int dir, void* values, void* buffer, void* stream)
 {
@@ -279,7 +337,8 @@ namespace
 // communication_object::allocate (include/ghex/communication_object.hpp:1019-1066)
 void plan_direction(const ghx_exchange_item* items, int n_items, bool receive,
                     std::vector<xbuffer>& bufs_out, std::vector<ghx_pack_entry>& sent,
-                    std::vector<ghx_upack_entry>& uent, std::vector<std::vector<ghx_box>>& box_store)
+                    std::vector<ghx_upack_entry>& uent, std::vector<std::vector<ghx_box>>& box_store,
+                    std::vector<const halo_entry*>* sent_halos = nullptr)
 {
     struct finfo
     {
@@ -372,6 +431,7 @@ void plan_direction(const ghx_exchange_item* items, int n_items, bool receive,
                 pe.boxes = bx.data();
                 pe.n_boxes = int32_t(bx.size());
                 sent.push_back(pe);
+                if (sent_halos) sent_halos->push_back(fi.e);
             }
             else
             {
@@ -531,6 +591,11 @@ int ghx_tune(const char* key, int32_t value)
         {
             if (value < 0 || value > 1) throw invalid("fast_addr must be 0 or 1");
             g_tune.fast_addr = value;
+        }
+        else if (k == "x_tile_elems")
+        {
+            if (value < 32 || value > 4096) throw invalid("x_tile_elems must be in [32, 4096]");
+            g_tune.x_tile_elems = uint32_t(value);
         }
         else if (k == "xcd_pair")
         {
@@ -868,6 +933,80 @@ int ghx_staged_pattern_create(int32_t dim, const ghx_regular_domain* domains, in
     });
 }
 
+static const ghx::halo_entry& key_of(const ghx_pattern* p, int32_t li, int32_t dir, int32_t key);
+
+int ghx_cs_halo_boxes(int32_t edge_size, int32_t levels, const ghx_cs_domain* domain,
+                      const int32_t* halos, ghx_box* local, ghx_box* global, int32_t* tiles,
+                      int32_t max_boxes, int32_t* n_boxes)
+{
+    return guarded([&] {
+        check_ptr(domain, "domain");
+        check_ptr(halos, "halos");
+        check_ptr(n_boxes, "n_boxes");
+        const auto b = cs_halo_boxes(edge_size, levels, *domain, halos);
+        *n_boxes = int32_t(b.size());
+        for (int32_t i = 0; i < std::min<int32_t>(max_boxes, int32_t(b.size())); ++i)
+        {
+            ghx_box l{}, g{};
+            for (int d = 0; d < 3; ++d)
+            {
+                l.first[d] = b[size_t(i)].b.lf[d];
+                l.last[d] = b[size_t(i)].b.ll[d];
+                g.first[d] = b[size_t(i)].b.gf[d];
+                g.last[d] = b[size_t(i)].b.gl[d];
+            }
+            if (local) local[i] = l;
+            if (global) global[i] = g;
+            if (tiles) tiles[i] = b[size_t(i)].tile;
+        }
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_pattern_create(int32_t edge_size, int32_t levels, const ghx_cs_domain* domains,
+                          int32_t n_domains, const int32_t* halos, int32_t my_rank,
+                          ghx_pattern** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        check_ptr(domains, "domains");
+        check_ptr(halos, "halos");
+        if (n_domains < 1) throw invalid("need at least one domain");
+        auto p = std::make_unique<ghx_pattern>();
+        cs_make_pattern(edge_size, levels, domains, n_domains, halos, my_rank, *p);
+        *out = p.release();
+        return GHX_OK;
+    });
+}
+
+int ghx_pattern_key_tiles(const ghx_pattern* p, int32_t local_index, int32_t direction,
+                          int32_t key, int32_t* tiles, int32_t max_boxes)
+{
+    return guarded([&] {
+        const auto& e = key_of(p, local_index, direction, key);
+        if (p->kind != 0 || p->cs_edge == 0) throw invalid("not a cubed-sphere pattern");
+        check_ptr(tiles, "tiles");
+        for (int32_t i = 0; i < std::min<int32_t>(max_boxes, int32_t(e.tiles.size())); ++i)
+            tiles[i] = e.tiles[size_t(i)];
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_unpack(const ghx_field_desc* field, const ghx_cs_item* cs, void* field_data,
+                  const void* buffer, const ghx_box* local, const ghx_box* global,
+                  const int32_t* tiles, int32_t n_boxes, ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(field, "field");
+        check_ptr(cs, "cs");
+        if (n_boxes < 0 || (n_boxes > 0 && (!local || !global || !tiles))) throw invalid("bad boxes");
+        check_cs_item(*field, *cs);
+        if (n_boxes == 0) return int(GHX_OK);
+        return run_cs_unpack(*field, *cs, local, global, tiles, n_boxes, field_data,
+                             const_cast<void*>(buffer), stream);
+    });
+}
+
 int ghx_pattern_filter(const ghx_pattern* p, const int32_t* ranks, int32_t n_ranks, int32_t keep,
                        ghx_pattern** out)
 {
@@ -1022,67 +1161,131 @@ int ghx_pattern_key_lids(const ghx_pattern* p, int32_t local_index, int32_t dire
 }
 
 // ---------------------------------------------------------------------------------- exchange
+// ghx_exchange_create (cs = null) and ghx_cs_exchange_create: with cubed-sphere items the
+// receive side is planned space by space (cs_plan_space) into the ordinary unpack plan and the
+// transformed one.
+static int make_exchange(const ghx_exchange_item* items, const ghx_cs_item* cs, int32_t n_items,
+                         ghx_exchange** out)
+{
+    check_ptr(out, "out");
+    if (n_items < 1 || !items) throw invalid("need at least one exchange item");
+    auto ex = std::make_unique<ghx_exchange>();
+    ex->n_items = n_items;
+    std::vector<ghx_pack_entry> rent;              // receive entries, for build_mixed
+    for (int dir = 0; dir < 2; ++dir)
+    {
+        const bool receive = dir == 1;
+        std::vector<ghx_pack_entry> sent;
+        std::vector<ghx_upack_entry> uent;
+        std::vector<std::vector<ghx_box>> store;
+        store.reserve(size_t(n_items) * 64);
+        auto& bufs = receive ? ex->recv : ex->send;
+        std::vector<const halo_entry*> halos;
+        plan_direction(items, n_items, receive, bufs, sent, uent, store, &halos);
+        // kept for per-buffer plans (ghx_exchange_split); moving the outer vector moves the
+        // inner ones, so the entries' box pointers stay valid
+        ex->box_store[dir] = std::move(store);
+        ex->entries[dir] = sent;
+        ex->uentries[dir] = uent;
+        if (receive) rent = sent;
+        if (receive && cs)
+        {
+            cs_recv_plan rp;
+            for (size_t k = 0; k < sent.size(); ++k)
+            {
+                const ghx_pack_entry& pe = sent[k];
+                const halo_entry& he = *halos[k];
+                if (he.tiles.size() != he.boxes.size())
+                    throw invalid("cubed-sphere exchange item whose pattern is not a cubed-sphere pattern");
+                uint64_t off = pe.buffer_offset;
+                for (size_t b = 0; b < he.boxes.size(); ++b)
+                {
+                    uint64_t nb = 0;
+                    cs_plan_space(rp, pe.field, cs[pe.field_slot], he.boxes[b], he.tiles[b],
+                                  pe.field_slot, pe.buffer_slot, off, &nb);
+                    off += nb;
+                }
+            }
+            ex->cs_rotated = rp.n_rotated;
+            if (!rp.segs.empty())
+                ex->sunpack = std::make_unique<splan>(std::move(rp.segs), rp.gf, rp.gb, rp.sbytes, 1);
+            if (!rp.xs.empty()) ex->xunpack = std::make_unique<xplan>(std::move(rp.xs));
+            continue;
+        }
+        if (!sent.empty())
+            (receive ? ex->sunpack : ex->spack) =
+                std::make_unique<splan>(sent.data(), int(sent.size()), receive ? 1 : 0);
+        if (!sent.empty() && g_tune.self_tile_bytes != g_tune.tile_bytes)
+        {
+            // candidate plans for the fused self exchange (kept only if it is fusable)
+            const uint32_t saved = g_tune.tile_bytes;
+            g_tune.tile_bytes = g_tune.self_tile_bytes;
+            try
+            {
+                (receive ? ex->self_unpack : ex->self_pack) =
+                    std::make_unique<splan>(sent.data(), int(sent.size()), receive ? 1 : 0);
+            }
+            catch (...)
+            {
+                g_tune.tile_bytes = saved;
+                throw;
+            }
+            g_tune.tile_bytes = saved;
+        }
+        if (!uent.empty())
+            (receive ? ex->uunpack : ex->upack) =
+                std::make_unique<uplan>(uent.data(), int(uent.size()), receive ? 1 : 0);
+    }
+    if (!ex->self_fusable() || !ex->self_pack || !ex->self_unpack ||
+        !exchange_plan::same_messages(*ex->self_pack, *ex->self_unpack))
+    {
+        ex->self_pack.reset();
+        ex->self_unpack.reset();
+    }
+    if (ex->self_fusable())
+    {
+        const splan& p = ex->self_pack ? *ex->self_pack : *ex->spack;
+        const splan& q = ex->self_unpack ? *ex->self_unpack : *ex->sunpack;
+        upload_pair_records(ex->self_recs, p.host_segs, q.host_segs, p.host_tiles);
+    }
+    if (ex->cs_rotated == 0) build_mixed(*ex, items[0].pattern->my_rank, rent);
+    *out = ex.release();
+    return GHX_OK;
+}
+
 int ghx_exchange_create(const ghx_exchange_item* items, int32_t n_items, ghx_exchange** out)
 {
+    return guarded([&] { return make_exchange(items, nullptr, n_items, out); });
+}
+
+int ghx_cs_exchange_create(const ghx_exchange_item* items, const ghx_cs_item* cs_items,
+                           int32_t n_items, ghx_exchange** out)
+{
     return guarded([&] {
-        check_ptr(out, "out");
+        check_ptr(cs_items, "cs_items");
         if (n_items < 1 || !items) throw invalid("need at least one exchange item");
-        auto ex = std::make_unique<ghx_exchange>();
-        ex->n_items = n_items;
-        std::vector<ghx_pack_entry> rent;              // receive entries, for build_mixed
-        for (int dir = 0; dir < 2; ++dir)
+        for (int32_t i = 0; i < n_items; ++i)
         {
-            const bool receive = dir == 1;
-            std::vector<ghx_pack_entry> sent;
-            std::vector<ghx_upack_entry> uent;
-            std::vector<std::vector<ghx_box>> store;
-            store.reserve(size_t(n_items) * 64);
-            auto& bufs = receive ? ex->recv : ex->send;
-            plan_direction(items, n_items, receive, bufs, sent, uent, store);
-            // kept for per-buffer plans (ghx_exchange_split); moving the outer vector moves the
-            // inner ones, so the entries' box pointers stay valid
-            ex->box_store[dir] = std::move(store);
-            ex->entries[dir] = sent;
-            ex->uentries[dir] = uent;
-            if (receive) rent = sent;
-            if (!sent.empty())
-                (receive ? ex->sunpack : ex->spack) =
-                    std::make_unique<splan>(sent.data(), int(sent.size()), receive ? 1 : 0);
-            if (!sent.empty() && g_tune.self_tile_bytes != g_tune.tile_bytes)
-            {
-                // candidate plans for the fused self exchange (kept only if it is fusable)
-                const uint32_t saved = g_tune.tile_bytes;
-                g_tune.tile_bytes = g_tune.self_tile_bytes;
-                try
-                {
-                    (receive ? ex->self_unpack : ex->self_pack) =
-                        std::make_unique<splan>(sent.data(), int(sent.size()), receive ? 1 : 0);
-                }
-                catch (...)
-                {
-                    g_tune.tile_bytes = saved;
-                    throw;
-                }
-                g_tune.tile_bytes = saved;
-            }
-            if (!uent.empty())
-                (receive ? ex->uunpack : ex->upack) =
-                    std::make_unique<uplan>(uent.data(), int(uent.size()), receive ? 1 : 0);
+            if (items[i].kind != 0) throw invalid("cubed-sphere exchange items are structured fields");
+            if (!items[i].pattern || items[i].pattern->cs_edge == 0)
+                throw invalid("cubed-sphere exchange item whose pattern is not a cubed-sphere pattern");
+            if (items[i].pattern->cs_edge != cs_items[i].edge_size)
+                throw invalid("cubed-sphere exchange item: edge_size differs from the pattern's");
+            check_cs_item(items[i].field, cs_items[i]);
         }
-        if (!ex->self_fusable() || !ex->self_pack || !ex->self_unpack ||
-            !exchange_plan::same_messages(*ex->self_pack, *ex->self_unpack))
-        {
-            ex->self_pack.reset();
-            ex->self_unpack.reset();
-        }
-        if (ex->self_fusable())
-        {
-            const splan& p = ex->self_pack ? *ex->self_pack : *ex->spack;
-            const splan& q = ex->self_unpack ? *ex->self_unpack : *ex->sunpack;
-            upload_pair_records(ex->self_recs, p.host_segs, q.host_segs, p.host_tiles);
-        }
-        build_mixed(*ex, items[0].pattern->my_rank, rent);
-        *out = ex.release();
+        return make_exchange(items, cs_items, n_items, out);
+    });
+}
+
+int ghx_cs_plan_info(const ghx_exchange* ex, int32_t* n_records, uint64_t* bytes,
+                     int32_t* n_tiles, int32_t* n_rotated)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        if (n_records) *n_records = ex->xunpack ? ex->xunpack->n_records : 0;
+        if (bytes) *bytes = ex->xunpack ? ex->xunpack->bytes : 0;
+        if (n_tiles) *n_tiles = ex->xunpack ? int32_t(ex->xunpack->n_tiles) : 0;
+        if (n_rotated) *n_rotated = ex->cs_rotated;
         return GHX_OK;
     });
 }
@@ -1147,6 +1350,9 @@ int ghx_exchange_unpack(const ghx_exchange* ex, void* const* field_ptrs, int32_t
         if (ex->sunpack) rc = ex->sunpack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
         if (rc == GHX_OK && ex->uunpack)
             rc = ex->uunpack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+        // cubed sphere: the transformed spaces, after the ordinary launch on the same stream
+        if (rc == GHX_OK && ex->xunpack)
+            rc = ex->xunpack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
         return rc;
     });
 }
@@ -1275,6 +1481,9 @@ int ghx_exchange_set_parity(ghx_exchange* ex, int32_t direction, const uint64_t*
     return guarded([&] {
         check_ptr(ex, "exchange");
         if (direction != 0 && direction != 1) throw invalid("direction must be 0 (pack) or 1 (unpack)");
+        if (direction == 1 && parity_word && ex->cs_rotated > 0)
+            throw invalid("double-buffered receive buffers are not available on a cubed-sphere "
+                          "exchange with rotated spaces (the transformed unpack reads one copy)");
         const size_t n = direction == 0 ? ex->send.size() : ex->recv.size();
         parity_cfg cfg;
         if (parity_word)

@@ -51,10 +51,19 @@ struct exchange_plan
     std::vector<std::unique_ptr<splan>> bplan[2];
     std::vector<std::unique_ptr<uplan>> ubplan[2];
     bool split = false;
+    // cubed sphere (ghx_cs_exchange_create): the transformed unpack launch, and the number of
+    // rotated receive spaces (those planned as ordinary segments included). With one rotated
+    // space the exchange is neither fused, mixed nor split: those paths unpack from `entries`,
+    // which know nothing of the rotation.
+    std::unique_ptr<xplan> xunpack;
+    int32_t cs_rotated = 0;
 
     void make_split()
     {
         if (split) return;
+        if (cs_rotated > 0)
+            throw invalid("per-buffer plans are not available on a cubed-sphere exchange with "
+                          "rotated spaces (the per-buffer unpack does not rotate)");
         for (int dir = 0; dir < 2; ++dir)
         {
             const size_t nb = dir == 0 ? send.size() : recv.size();
@@ -107,7 +116,7 @@ struct exchange_plan
     bool self_fusable() const
     {
         if (self_ok >= 0) return self_ok == 1;
-        bool ok = !upack && !uunpack && spack && sunpack && send.size() == recv.size() &&
+        bool ok = cs_rotated == 0 && !upack && !uunpack && spack && sunpack && send.size() == recv.size() &&
                   !spack->grouped() && !sunpack->grouped();
         for (size_t i = 0; ok && i < send.size(); ++i)
             ok = send[i].first_id == recv[i].first_id && send[i].second_id == recv[i].second_id &&

@@ -64,6 +64,9 @@ struct tuning
     int tile_records = 1;              // k_copy reads per tile ONE record (its segment with the
                                        // tile index in first_tile) at blockIdx: no dependent
                                        // tile-table load ahead of the segment load
+    uint32_t x_tile_elems = 256;       // elements per tile of transformed (cubed-sphere)
+                                       // segments: one per lane (512 and 1024
+                                       // lost to the element-row form, 128 ties 256)
     int fast_addr = 1;                 // structured segments whose offsets fit the short form
                                        // (seg_s::amode) decode rows with 1-2 divisions and
                                        // full-rate 24-bit products instead of int64 ones
@@ -151,6 +154,51 @@ struct alignas(16) seg_u
 };
 static_assert(sizeof(seg_u) == 96, "seg_u layout");
 
+// Transformed segment (cubed sphere): an iteration space received from another
+// cube tile whose rotation moves or reverses the field's stride-1 axis, or negates a vector
+// component (cubed_sphere/field_descriptor.hpp:81-108). The buffer holds the dense box in the
+// NEIGHBOUR's coordinates, row-major in the field's layout order; each buffer axis has a signed
+// field byte stride. `xseg` is the planner's description of the whole box (axes in buffer order,
+// 0 = fastest); `seg_x` is the record of ONE workgroup tile of it (k_unpack_x reads the record at
+// its block index): a sub-box of about one element per lane that is wide along BOTH the
+// buffer's fastest axis and the field's, walked with its axes sorted by ascending |field
+// stride| — a wave reads a few long buffer row pieces and writes whole field runs, so neither
+// side is walked element by element across lines.
+struct xseg
+{
+    int64_t field_off;   // field byte offset of buffer cell (0, 0, 0, 0)
+    uint64_t buf_off;    // byte offset of the box in its buffer
+    int64_t stride[4];   // signed field byte stride per buffer axis
+    uint32_t ext[4];     // extents in buffer order (1 for unused axes)
+    uint32_t elem;       // 1, 2, 4, 8 or 16 bytes
+    int32_t comp_axis;   // the buffer axis that is the component axis (-1: none)
+    uint8_t neg_mask;    // bit k: component k is negated (k = 0, 1)
+    uint8_t neg_kind;    // 1: IEEE sign-bit flip, 2: two's-complement negate
+    int32_t field_slot, buf_slot;  // the caller's slots
+    uint32_t tile_elems; // the planner's tile size in elements
+    uint64_t bytes() const { return uint64_t(ext[0]) * ext[1] * ext[2] * ext[3] * elem; }
+};
+
+struct alignas(16) seg_x
+{
+    int64_t field_off;    // field byte offset of the tile's first cell
+    uint64_t buf_off;     // byte offset of the tile's first cell in its buffer
+    int64_t stride[4];    // field byte stride per tile axis; axes by ascending |stride|
+    uint32_t tdim[4];     // the plan's tile extents per axis (decode radix)
+    uint32_t act[4];      // this tile's extents (<= tdim: the last tile along an axis)
+    uint32_t bstride[4];  // element stride of the axis in the buffer's dense box
+    magic_u32 mag[4];     // division by tdim[k]
+    uint32_t bytes;       // bytes this tile moves
+    uint32_t comp0;       // component index of the tile's first cell
+    uint16_t field_slot;
+    uint16_t buf_slot;
+    uint8_t elog2;        // log2 of the element size
+    uint8_t comp_pos;     // which of the four axes is the component axis (4: none)
+    uint8_t neg_mask;
+    uint8_t neg_kind;
+};
+static_assert(sizeof(seg_x) == 144, "seg_x layout");
+
 // Kernel arguments (passed by value: <= 1.7 KB of kernarg).
 struct kargs
 {
@@ -199,6 +247,7 @@ int launch_structured(const kargs& a, int direction, void* stream, uint32_t grid
 int launch_unstructured(const kargs& a, int direction, void* stream, uint32_t grid, bool runs);
 int launch_self(const kargs& a, void* stream, uint32_t grid);
 int launch_put(const kargs& a, void* stream, uint32_t grid);
+int launch_unpack_x(const kargs& a, void* stream, uint32_t grid);  // tile_recs: seg_x records
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

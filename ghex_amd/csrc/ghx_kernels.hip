@@ -918,6 +918,107 @@ __global__ __launch_bounds__(kBlock) void k_put(kargs a)
     }
 }
 
+// Transformed unpack (cubed sphere): one workgroup per tile record (seg_x).
+//
+// The tile is a sub-box of the buffer's dense box (the halo in the neighbour tile's
+// coordinates), about one element per lane, walked in FIELD order: the record's axes are sorted
+// by ascending |field stride|, so consecutive lanes write consecutive field elements of one run
+// and a wave's store covers whole runs, while its loads fall on a few long pieces of buffer rows
+// (for an x-stride-1 field and a halo of width H rotated by 90 degrees: H buffer rows of up to
+// 256 / H elements each, written as H-element field runs, where the element-row form of the
+// ordinary kernel issues one store per line). A reversed axis is a negative stride. Vector
+// components are negated in registers between the load and the store
+// (cubed_sphere/field_descriptor.hpp:97-104): sign-bit flip (neg_kind 1) or two's-complement
+// negate (2) of component 0 / 1 by neg_mask. Staging the tile through LDS (buffer range read
+// lane-linear, transposed reads from LDS) measured slower at every tile size: the launch is
+// latency-bound and the LDS round trip and its barrier sit in the dependent chain.
+template<int E>
+__device__ __forceinline__ void unpack_x_tile(const seg_x& s, const char* __restrict__ src,
+                                              char* __restrict__ field, bool aligned)
+{
+    using V = typename vec_t<(1 << E)>::type;
+    const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
+    for (uint32_t i = threadIdx.x; i < total; i += kBlock)
+    {
+        const uint32_t q0 = fastdiv(i, s.mag[0]);
+        const uint32_t c0 = i - q0 * s.tdim[0];
+        const uint32_t q1 = fastdiv(q0, s.mag[1]);
+        const uint32_t c1 = q0 - q1 * s.tdim[1];
+        const uint32_t c3 = fastdiv(q1, s.mag[2]);
+        const uint32_t c2 = q1 - c3 * s.tdim[2];
+        if (c0 >= s.act[0] || c1 >= s.act[1] || c2 >= s.act[2] || c3 >= s.act[3]) continue;
+        const uint32_t bi = c0 * s.bstride[0] + c1 * s.bstride[1] + c2 * s.bstride[2] +
+                            c3 * s.bstride[3];
+        const char* from = src + (size_t(bi) << E);
+        V v;
+        if (aligned) v = vload<V>(from);
+        else
+        {
+            // a buffer or field whose base or strides are not multiples of the element size
+            unsigned char b[1 << E];
+#pragma unroll
+            for (int k = 0; k < (1 << E); ++k) b[k] = vload<unsigned char>(from + k);
+            __builtin_memcpy(&v, b, sizeof(V));
+        }
+        if (s.neg_mask)
+        {
+            uint32_t comp = s.comp0;
+            if (s.comp_pos < 4) comp += s.comp_pos == 0 ? c0 : s.comp_pos == 1 ? c1 : s.comp_pos == 2 ? c2 : c3;
+            if (comp < 2 && ((s.neg_mask >> comp) & 1u))
+            {
+                if constexpr (E == 2)
+                    v = s.neg_kind == 1 ? (v ^ 0x80000000u) : (0u - v);
+                else if constexpr (E == 3)
+                {
+                    if (s.neg_kind == 1) v.y ^= 0x80000000u;
+                    else
+                    {
+                        const uint64_t w = 0ull - ((uint64_t(v.y) << 32) | v.x);
+                        v.x = uint32_t(w);
+                        v.y = uint32_t(w >> 32);
+                    }
+                }
+            }
+        }
+        char* dst = field + s.field_off + int64_t(c0) * s.stride[0] + int64_t(c1) * s.stride[1] +
+                    int64_t(c2) * s.stride[2] + int64_t(c3) * s.stride[3];
+        if (aligned) vstore<V>(dst, v);
+        else
+        {
+            unsigned char b[1 << E];
+            __builtin_memcpy(b, &v, sizeof(V));
+#pragma unroll
+            for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(dst + k, b[k]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_unpack_x(kargs a)
+{
+    const seg_x* __restrict__ recs = static_cast<const seg_x*>(a.tile_recs);
+    for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x)
+    {
+        const seg_x s = recs[t];
+        const char* src = reinterpret_cast<const char*>(a.buf_ptr[s.buf_slot]) + s.buf_off;
+        char* field = reinterpret_cast<char*>(a.field_ptr[s.field_slot]);
+        // element-wide accesses when both sides are element-aligned (uniform per tile)
+        const uint64_t em = (1u << s.elog2) - 1u;
+        const bool aligned =
+            (reinterpret_cast<uint64_t>(src) & em) == 0 &&
+            ((reinterpret_cast<uint64_t>(field) + uint64_t(s.field_off)) & em) == 0 &&
+            ((uint64_t(s.stride[0]) | uint64_t(s.stride[1]) | uint64_t(s.stride[2]) |
+              uint64_t(s.stride[3])) & em) == 0;
+        switch (s.elog2)
+        {
+            case 4: unpack_x_tile<4>(s, src, field, aligned); break;
+            case 3: unpack_x_tile<3>(s, src, field, aligned); break;
+            case 2: unpack_x_tile<2>(s, src, field, aligned); break;
+            case 1: unpack_x_tile<1>(s, src, field, aligned); break;
+            default: unpack_x_tile<0>(s, src, field, aligned); break;
+        }
+    }
+}
+
 int launched(const char* what)
 {
     const hipError_t e = hipGetLastError();
@@ -1022,6 +1123,13 @@ int launch_put(const kargs& a, void* stream, uint32_t grid)
     if (a.tile_recs) launch(k_put<true>, grid, static_cast<hipStream_t>(stream), a);
     else launch(k_put<false>, grid, static_cast<hipStream_t>(stream), a);
     return launched("put");
+}
+
+int launch_unpack_x(const kargs& a, void* stream, uint32_t grid)
+{
+    if (a.n_tiles == 0) return GHX_OK;
+    launch(k_unpack_x, min(grid, a.n_tiles), static_cast<hipStream_t>(stream), a);
+    return launched("transformed unpack");
 }
 
 template<bool DBL, bool REC>

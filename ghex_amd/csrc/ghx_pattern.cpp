@@ -98,11 +98,6 @@ int regular_make_pattern(int dim, const ghx_regular_domain* doms, int n, const i
     }
     // recv halos of every domain (all ranks: the receivers assign the tags that the senders'
     // keys carry): boxes x ranks x domains, keyed by the remote domain id (pattern.hpp:290-329)
-    struct recv_map
-    {
-        std::map<int32_t, std::pair<int32_t, std::vector<is_pair>>> by_id;  // id -> (rank, IS)
-        std::vector<halo_entry> entries;                                    // with tags
-    };
     std::vector<recv_map> recv(n);
     for (int a = 0; a < n; ++a)
     {
@@ -124,12 +119,29 @@ int regular_make_pattern(int dim, const ghx_regular_domain* doms, int n, const i
                         if (x.gf[c] > x.gl[c]) ok = false;
                     }
                     if (!ok) continue;
-                    auto it = recv[a].by_id.find(o.id);
-                    if (it == recv[a].by_id.end())
-                        it = recv[a].by_id.emplace(o.id, std::make_pair(o.rank, std::vector<is_pair>{})).first;
-                    it->second.second.push_back(x);
+                    auto& sp = recv[a].by_id[o.id];
+                    sp.rank = o.rank;
+                    sp.boxes.push_back(x);
                 }
     }
+    std::vector<pattern_domain> pd(static_cast<size_t>(n));
+    for (int a = 0; a < n; ++a)
+    {
+        pd[a].id = doms[a].id;
+        pd[a].rank = doms[a].rank;
+        for (int c = 0; c < 3; ++c) pd[a].first[c] = c < dim ? doms[a].first[c] : 0;
+    }
+    return finish_structured_pattern(dim, pd, recv, my_rank, out);
+}
+
+int finish_structured_pattern(int dim, const std::vector<pattern_domain>& doms,
+                              std::vector<recv_map>& recv, int my_rank, pattern_set& out)
+{
+    const int n = int(doms.size());
+    int world = 0;
+    for (int i = 0; i < n; ++i) world = std::max(world, doms[i].rank + 1);
+    std::vector<std::vector<int>> by_rank(world);
+    for (int i = 0; i < n; ++i) by_rank[doms[i].rank].push_back(i);
     // tags: per receiving rank, per remote rank 0,1,2,... over its patterns in order, each
     // pattern's map in key order (pattern.hpp:331-367)
     int32_t max_tag = 0;
@@ -139,7 +151,7 @@ int regular_make_pattern(int dim, const ghx_regular_domain* doms, int n, const i
         for (int a : by_rank[r])
             for (auto& kv : recv[a].by_id)
             {
-                const int32_t rr = kv.second.first;
+                const int32_t rr = kv.second.rank;
                 int32_t tag;
                 auto it = tag_map.find(rr);
                 if (it == tag_map.end())
@@ -154,7 +166,8 @@ int regular_make_pattern(int dim, const ghx_regular_domain* doms, int n, const i
                 }
                 halo_entry e;
                 e.key = {kv.first, rr, tag};
-                e.boxes = kv.second.second;
+                e.boxes = kv.second.boxes;
+                e.tiles = kv.second.tiles;
                 recv[a].entries.push_back(std::move(e));
             }
     }
@@ -187,6 +200,7 @@ int regular_make_pattern(int dim, const ghx_regular_domain* doms, int n, const i
                     }
                     s.boxes.push_back(x);
                 }
+                s.tiles = e.tiles;
                 send.emplace(std::make_pair(s.key.remote_id, s.key.tag), std::move(s));
             }
         for (auto& kv : send) p.send.push_back(std::move(kv.second));

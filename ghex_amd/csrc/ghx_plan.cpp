@@ -521,6 +521,29 @@ splan::splan(const ghx_pack_entry* entries, int n_entries, int dir) : direction(
         gb.resize(segs.size(), en.buffer_slot);
         bytes += off - en.buffer_offset;
     }
+    build(segs, gf, gb);
+}
+
+splan::splan(std::vector<seg_s> segs, const std::vector<int32_t>& gf, const std::vector<int32_t>& gb,
+             uint64_t nbytes, int dir)
+: direction(dir)
+{
+    tile_bytes = g_tune.tile_bytes;
+    if (dir != 0 && dir != 1) throw invalid("direction must be 0 (pack) or 1 (unpack)");
+    if (gf.size() != segs.size() || gb.size() != segs.size()) throw invalid("one slot pair per segment");
+    for (size_t k = 0; k < segs.size(); ++k)
+    {
+        if (gf[k] < 0 || gb[k] < 0) throw invalid("negative slot");
+        max_field_slot = std::max(max_field_slot, gf[k]);
+        max_buf_slot = std::max(max_buf_slot, gb[k]);
+    }
+    bytes = nbytes;
+    build(segs, gf, gb);
+}
+
+void splan::build(const std::vector<seg_s>& segs, const std::vector<int32_t>& gf,
+                  const std::vector<int32_t>& gb)
+{
     n_segments = int32_t(segs.size());
     const slot_partition part = partition_slots(gf, gb);
     for (size_t g = 0; g < part.segs.size(); ++g)
@@ -582,6 +605,158 @@ int splan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* s
     int rc = run(dev, n_tiles, fmap, bmap);
     for (size_t g = 0; rc == GHX_OK && g < more.size(); ++g)
         rc = run(more[g]->dev, more[g]->n_tiles, more[g]->fmap, more[g]->bmap);
+    return rc;
+}
+
+void finish_segment(seg_s& s)
+{
+    s.mag_row = make_magic(s.row_bytes);
+    for (int k = 0; k < 3; ++k) s.mag_ext[k] = make_magic(s.ext[k]);
+    const int wb = std::min(wlog2_of(uint64_t(s.row_bytes)), wlog2_of(s.buf_off));
+    int wf = wlog2_of(uint64_t(s.field_off));
+    for (int k = 0; k < s.n_outer; ++k)
+        if (s.ext[k] > 1) wf = std::min(wf, wlog2_of(uint64_t(s.stride[k] < 0 ? -s.stride[k] : s.stride[k])));
+    s.wlog2 = uint8_t(std::min(wb, wf));
+    s.amode = short_addressing(s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// transformed unpack (cubed sphere)
+// ---------------------------------------------------------------------------------------------
+// Tile shape: about tile_elems elements (one per lane) as a sub-box that is wide along both
+// the buffer's fastest axis (coalesced reads) and the field's fastest axis (whole field runs per
+// wave store): up to 16 elements of the field's axis first, the rest of the budget along the
+// buffer's, what is left back to the field's and then to the other axes in buffer order; the
+// chunks of an axis are evened out. When the two axes coincide (only a component is negated)
+// the axes are filled in buffer order. The store side walks the tile with its axes sorted by
+// ascending |field stride| (axes of extent 1 last).
+void make_tile_records(std::vector<seg_x>& out, const xseg& b, uint16_t field_slot,
+                       uint16_t buf_slot)
+{
+    if (b.elem < 1 || b.elem > 16 || (b.elem & (b.elem - 1))) throw invalid("transformed segment: element size");
+    if (b.bytes() == 0 || b.bytes() >= (uint64_t(1) << 31)) throw invalid("transformed segment: box size");
+    auto mag = [&](int k) { return uint64_t(b.stride[k] < 0 ? -b.stride[k] : b.stride[k]); };
+    const uint64_t budget = std::max<uint32_t>(1, b.tile_elems);
+    uint32_t t[4] = {1, 1, 1, 1};
+    int ba = -1, fa = -1;
+    for (int k = 0; k < 4; ++k)
+    {
+        if (b.ext[k] <= 1) continue;
+        if (ba < 0) ba = k;
+        if (fa < 0 || mag(k) < mag(fa)) fa = k;
+    }
+    uint64_t room = budget;
+    if (ba >= 0 && fa != ba)
+    {
+        t[fa] = uint32_t(std::min<uint64_t>(b.ext[fa], 16));
+        t[ba] = uint32_t(std::min<uint64_t>(b.ext[ba], std::max<uint64_t>(1, budget / t[fa])));
+        t[fa] = uint32_t(std::min<uint64_t>(b.ext[fa], std::max<uint64_t>(1, budget / t[ba])));
+        room = std::max<uint64_t>(1, budget / (uint64_t(t[fa]) * t[ba]));
+    }
+    for (int k = 0; k < 4; ++k)
+    {
+        if (ba >= 0 && fa != ba && (k == fa || k == ba)) continue;
+        t[k] = uint32_t(std::min<uint64_t>(b.ext[k], std::max<uint64_t>(1, room)));
+        room = std::max<uint64_t>(1, room / t[k]);
+    }
+    for (int k = 0; k < 4; ++k)
+    {
+        const uint32_t chunks = (b.ext[k] + t[k] - 1) / t[k];
+        t[k] = (b.ext[k] + chunks - 1) / chunks;
+    }
+    int perm[4] = {0, 1, 2, 3};
+    std::stable_sort(perm, perm + 4, [&](int x, int y) {
+        if ((t[x] == 1) != (t[y] == 1)) return t[y] == 1;
+        return mag(x) < mag(y);
+    });
+    const uint32_t bs[4] = {1, b.ext[0], b.ext[0] * b.ext[1], b.ext[0] * b.ext[1] * b.ext[2]};
+    int elog2 = 0;
+    while ((1u << elog2) < b.elem) ++elog2;
+    uint32_t o[4];
+    for (o[3] = 0; o[3] < b.ext[3]; o[3] += t[3])
+        for (o[2] = 0; o[2] < b.ext[2]; o[2] += t[2])
+            for (o[1] = 0; o[1] < b.ext[1]; o[1] += t[1])
+                for (o[0] = 0; o[0] < b.ext[0]; o[0] += t[0])
+                {
+                    seg_x r{};
+                    r.field_off = b.field_off;
+                    uint64_t lin = 0, n = 1;
+                    for (int k = 3; k >= 0; --k) lin = lin * b.ext[k] + o[k];
+                    for (int k = 0; k < 4; ++k) r.field_off += int64_t(o[k]) * b.stride[k];
+                    r.buf_off = b.buf_off + lin * b.elem;
+                    r.comp_pos = 4;
+                    for (int j = 0; j < 4; ++j)
+                    {
+                        const int k = perm[j];
+                        r.stride[j] = b.stride[k];
+                        r.tdim[j] = t[k];
+                        r.act[j] = std::min(t[k], b.ext[k] - o[k]);
+                        r.bstride[j] = bs[k];
+                        r.mag[j] = make_magic(t[k]);
+                        n *= r.act[j];
+                        if (k == b.comp_axis) r.comp_pos = uint8_t(j);
+                    }
+                    r.bytes = uint32_t(n * b.elem);
+                    r.comp0 = b.comp_axis >= 0 ? o[b.comp_axis] : 0;
+                    r.field_slot = field_slot;
+                    r.buf_slot = buf_slot;
+                    r.elog2 = uint8_t(elog2);
+                    r.neg_mask = b.neg_mask;
+                    r.neg_kind = b.neg_kind;
+                    out.push_back(r);
+                }
+}
+
+xplan::xplan(std::vector<xseg> bx) : boxes(std::move(bx))
+{
+    std::vector<int32_t> gf, gb;
+    for (const xseg& b : boxes)
+    {
+        if (b.field_slot < 0 || b.buf_slot < 0) throw invalid("negative slot");
+        max_field_slot = std::max(max_field_slot, b.field_slot);
+        max_buf_slot = std::max(max_buf_slot, b.buf_slot);
+        gf.push_back(b.field_slot);
+        gb.push_back(b.buf_slot);
+        bytes += b.bytes();
+    }
+    n_records = int32_t(boxes.size());
+    const slot_partition part = partition_slots(gf, gb);
+    for (size_t g = 0; g < part.segs.size(); ++g)
+    {
+        auto grp = std::make_unique<group>();
+        grp->fmap = part.fmap[g];
+        grp->bmap = part.bmap[g];
+        for (uint32_t k : part.segs[g])
+            make_tile_records(grp->host, boxes[k], uint16_t(part.lf[k]), uint16_t(part.lb[k]));
+        n_tiles += uint32_t(grp->host.size());
+        if (!grp->host.empty() && have_device())
+        {
+            const size_t rb = grp->host.size() * sizeof(seg_x);
+            if (hipMalloc(&grp->dev.recs, rb) != hipSuccess) throw hip_error("hipMalloc(transformed records)");
+            if (hipMemcpy(grp->dev.recs, grp->host.data(), rb, hipMemcpyHostToDevice) != hipSuccess)
+                throw hip_error("hipMemcpy(transformed records)");
+        }
+        groups.push_back(std::move(grp));
+    }
+}
+
+int xplan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
+{
+    if (n_tiles == 0) return GHX_OK;
+    if (nf <= max_field_slot || nb <= max_buf_slot) throw invalid("pointer arrays do not cover the plan's slots");
+    int rc = GHX_OK;
+    for (size_t g = 0; rc == GHX_OK && g < groups.size(); ++g)
+    {
+        const group& grp = *groups[g];
+        if (grp.host.empty()) continue;
+        if (!grp.dev.recs) throw hip_error("plan has no device tables (no HIP device at creation)");
+        kargs a{};
+        a.tile_recs = grp.dev.recs;
+        a.n_tiles = uint32_t(grp.host.size());
+        fill_slots(a.field_ptr, fptr, grp.fmap, max_field_slot + 1, "field");
+        fill_slots(a.buf_ptr, bptr, grp.bmap, max_buf_slot + 1, "buffer");
+        rc = launch_unpack_x(a, stream, grid_for_tiles(a.n_tiles));
+    }
     return rc;
 }
 

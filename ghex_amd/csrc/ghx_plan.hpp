@@ -43,6 +43,9 @@ void upload_pair_records(device_tables& dt, const std::vector<seg_s>& primary,
                          const std::vector<seg_s>& companion, const std::vector<uint32_t>& tiles);
 uint64_t add_box_segments(std::vector<seg_s>& out, const ghx_field_desc& f, const ghx_box& box,
                           uint16_t field_slot, uint16_t buf_slot, uint64_t buf_off);
+// the derived members of a segment built by hand (divisors, vector width, addressing form) from
+// its offsets, strides, extents, row length and byte count
+void finish_segment(seg_s& s);
 
 // Launch groups. A launch carries at most GHX_MAX_SLOTS field and buffer pointers (kargs is
 // passed by value); a plan whose entries use more slots than that (many fields in one exchange,
@@ -77,8 +80,39 @@ struct splan
     bool grouped() const { return !fmap.empty() || !bmap.empty() || !more.empty(); }
     uint32_t total_tiles() const;
     splan(const ghx_pack_entry* entries, int n_entries, int direction);
+    // from ready segments (cubed sphere: rotated spaces that keep contiguous rows): gf / gb are
+    // the caller's field / buffer slot of each segment, `bytes` the buffer bytes they cover
+    splan(std::vector<seg_s> segs, const std::vector<int32_t>& gf, const std::vector<int32_t>& gb,
+          uint64_t bytes, int direction);
+    // launch groups, tile tables and device tables of the plan's segments (both constructors)
+    void build(const std::vector<seg_s>& segs, const std::vector<int32_t>& gf,
+               const std::vector<int32_t>& gb);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
+
+// transformed unpack plan (cubed sphere): the tile records of its xseg boxes, cut into launch
+// groups of at most GHX_MAX_SLOTS field and buffer slots like the other plans. One k_unpack_x
+// launch per group, enqueued after the ordinary unpack launch on the same stream.
+struct xplan
+{
+    uint64_t bytes = 0;
+    int32_t n_records = 0;     // boxes
+    uint32_t n_tiles = 0;      // of all groups
+    int max_field_slot = -1, max_buf_slot = -1;  // caller slots
+    std::vector<xseg> boxes;
+    struct group
+    {
+        std::vector<int32_t> fmap, bmap;
+        std::vector<seg_x> host;
+        device_tables dev;     // dev.recs: the records
+    };
+    std::vector<std::unique_ptr<group>> groups;
+    explicit xplan(std::vector<xseg> boxes);
+    int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
+};
+// the tile records of one box (local slots as given)
+void make_tile_records(std::vector<seg_x>& out, const xseg& b, uint16_t field_slot,
+                       uint16_t buf_slot);
 
 // unstructured fused plan
 struct uplan

@@ -88,6 +88,16 @@ class PatternContainer:
             out.append((rid, rr, tag, sp))
         return out
 
+    def halo_tiles(self, local_index: int, direction: int):
+        """Cubed-sphere patterns: per key of halos(local_index, direction) the tile of each
+        iteration space's global box (ghx_pattern_key_tiles)."""
+        out = []
+        for k, rid, rr, tag, ns, ne in self._keys(local_index, direction):
+            arr = (ctypes.c_int32 * max(1, ns))()
+            _ghx.call("ghx_pattern_key_tiles", self._h, local_index, direction, k, arr, ns)
+            out.append(list(arr[:ns]))
+        return out
+
     def lid_arrays(self, local_index: int, direction: int):
         """Unstructured: halos(local_index, direction) with each lid list as an int64 numpy
         array (no Python list of ints)."""

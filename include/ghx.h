@@ -60,7 +60,9 @@ typedef void* ghx_stream;
  * "unpack_tile_bytes" (0 = tile_bytes, the default; else the long-row tile of unpack plans, whose
  * tiles of several steps the unpack kernel then software-pipelines);
  * "fast_addr" (0|1: short-form 32-bit field addressing for segments whose extents, strides and
- * span fit it; default 1), "pack_tile_rows" / "unpack_tile_rows" (0 = by the plan's rule, the
+ * span fit it; default 1), "x_tile_elems" (elements per workgroup tile of the cubed-sphere
+ * transformed unpack, 32..4096; default 256, one per lane), "pack_tile_rows" /
+ * "unpack_tile_rows" (0 = by the plan's rule, the
  * default; else 64..65536 rows per tile of short-row structured segments of pack / unpack plans);
  * "reset" restores every default. Plan-shaping knobs apply to plans created afterwards. Unknown
  * keys fail with GHX_ERR_INVALID (the variants removed in round 3 are listed in
@@ -356,6 +358,49 @@ int ghx_pattern_key_lids(const ghx_pattern* p, int32_t local_index, int32_t dire
                          int32_t key, int64_t* lids, int64_t max_lids);
 
 /* ------------------------------------------------------------------------------------------
+ * Cubed-sphere grids (include/ghex/structured/cubed_sphere/): six tiles of edge_size x edge_size
+ * cells over `levels` levels, oriented as drawn in cubed_sphere/transform.hpp:21-38. A halo that
+ * crosses a cube edge arrives in the neighbour tile's coordinates and is rotated (and, for
+ * vector fields, sign-flipped) into the receiver's by the unpack
+ * (cubed_sphere/field_descriptor.hpp:55-109, 142-167).
+ * ------------------------------------------------------------------------------------------ */
+
+/* cubed_sphere::domain_descriptor(cube, tile, x_first, x_last, y_first, y_last)
+ * (cubed_sphere/domain_descriptor.hpp:92-104) of one rank; all levels. The library computes
+ * the domain's int32 id as (tile * edge_size + y_first) * edge_size + x_first, whose integer
+ * order is the order of the reference's (tile, (x_first, y_first)) ids (:33-61). */
+typedef struct ghx_cs_domain
+{
+    int32_t rank;
+    int32_t tile;
+    int32_t x_first, x_last;
+    int32_t y_first, y_last;
+} ghx_cs_domain;
+
+/* cubed_sphere::halo_generator::operator() (cubed_sphere/halo_generator.hpp:75-198): the receive
+ * boxes of one domain in the reference's order, local and global coordinates (x, y, z) and the
+ * tile of each global box (the domain's own or an edge neighbour's, whose coordinates the
+ * global box is then given in). halos = the four widths as the code applies them: -x, +x, -y,
+ * +y. Query the count with max_boxes = 0. `rank` of the domain is ignored. */
+int ghx_cs_halo_boxes(int32_t edge_size, int32_t levels, const ghx_cs_domain* domain,
+                      const int32_t* halos, ghx_box* local, ghx_box* global, int32_t* tiles,
+                      int32_t max_boxes, int32_t* n_boxes);
+
+/* make_pattern<structured::grid> (include/ghex/structured/pattern.hpp:214-571) with the
+ * cubed-sphere halo generator and its seven-argument intersect (halo_generator.hpp:227-283),
+ * for rank `my_rank` from ALL ranks' domains (ordered by rank, then each rank's d_range order).
+ * The result is an ordinary 3-D structured pattern (every ghx_pattern_* query works on it);
+ * ghx_pattern_key_tiles adds the tile of each iteration space's global box. Send boxes are in
+ * the sender's coordinates, so packing is the ordinary pack. */
+int ghx_cs_pattern_create(int32_t edge_size, int32_t levels, const ghx_cs_domain* domains,
+                          int32_t n_domains, const int32_t* halos, int32_t my_rank,
+                          ghx_pattern** out);
+/* The tile of the global box of each iteration space of a key (same order as
+ * ghx_pattern_key_boxes); GHX_ERR_INVALID on a pattern that is not a cubed-sphere one. */
+int ghx_pattern_key_tiles(const ghx_pattern* p, int32_t local_index, int32_t direction,
+                          int32_t key, int32_t* tiles, int32_t max_boxes);
+
+/* ------------------------------------------------------------------------------------------
  * Exchange planning: communication_object::allocate semantics (buffer per domain pair, fields
  * in exchange() order, alignof padding, tag = pattern tag + container tag offset)
  * (include/ghex/communication_object.hpp:483-566, 1003-1067).
@@ -474,6 +519,46 @@ int ghx_exchange_unpack_peers(const ghx_exchange* ex, void* const* field_ptrs, i
  * equivalent (its RMA path puts field to field, include/ghex/structured/rma_put.hpp:204-245). */
 int ghx_exchange_set_parity(ghx_exchange* ex, int32_t direction, const uint64_t* parity_word,
                             uint32_t parity_add, const int64_t* offsets, int32_t n_buffers);
+
+/* Cubed-sphere exchanges. cs_items[i] goes with items[i] (a structured item whose pattern came
+ * from ghx_cs_pattern_create): the field's domain (tile, first x / y cell, the cube's edge
+ * size), is_vector (cubed_sphere::field_descriptor's is_vector_field) and the value kind that
+ * says how a vector component is negated: 0 = opaque bits (scalar fields only), 1 = IEEE float
+ * of elem_size 4 / 8 (sign-bit flip), 2 = signed integer of elem_size 4 / 8 (two's-complement
+ * negate). A vector field of any other value type is refused (GHX_ERR_INVALID).
+ * The result is an ordinary ghx_exchange: buffers, sizes, tags and ghx_exchange_pack are those
+ * of ghx_exchange_create; ghx_exchange_unpack enqueues the ordinary unpack launch and then, on
+ * the same stream, the transformed one (k_unpack_x) for the spaces received from another tile
+ * whose rotation moves or reverses the field's stride-1 axis or negates a component. Rotated
+ * spaces that keep contiguous rows (z or the component stride-1) ride the ordinary launch.
+ * With one transformed (rotated) space ghx_exchange_self_fusable and ghx_exchange_mixed report
+ * 0, and ghx_exchange_split and ghx_exchange_set_parity(direction 1) fail with GHX_ERR_INVALID:
+ * the per-buffer, pipelined and double-buffered unpacks do not rotate. ghx_put_create sees
+ * fields and boxes only and has no cubed-sphere form: do not build puts from such a pattern
+ * (the Python bulk object refuses). */
+typedef struct ghx_cs_item
+{
+    int32_t tile;
+    int32_t first_x, first_y;
+    int32_t edge_size;
+    int32_t is_vector;
+    int32_t value_kind;
+} ghx_cs_item;
+int ghx_cs_exchange_create(const ghx_exchange_item* items, const ghx_cs_item* cs_items,
+                           int32_t n_items, ghx_exchange** out);
+/* The transformed part of an exchange's unpack (ghx_plan_info / ghx_plan_segment describe the
+ * ordinary part only): number of transformed-segment records (one per rotated iteration space
+ * and field), their buffer bytes and workgroup tiles, and the number of rotated spaces in all
+ * (those planned as ordinary segments included). Works on exchanges created without a device. */
+int ghx_cs_plan_info(const ghx_exchange* ex, int32_t* n_records, uint64_t* bytes,
+                     int32_t* n_tiles, int32_t* n_rotated);
+/* cubed_sphere::field_descriptor::unpack(const T* buffer, const IndexContainer& c, void* arg)
+ * (cubed_sphere/field_descriptor.hpp:142-167) for ONE field: iteration spaces back to back from
+ * `buffer`, each with its local box, global box and the global box's tile. Convenience form
+ * (cached plan), next to ghx_structured_unpack. */
+int ghx_cs_unpack(const ghx_field_desc* field, const ghx_cs_item* cs, void* field_data,
+                  const void* buffer, const ghx_box* local, const ghx_box* global,
+                  const int32_t* tiles, int32_t n_boxes, ghx_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Zero-copy put between node-local GPUs. Replaces the reference's RMA path:
