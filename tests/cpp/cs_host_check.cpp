@@ -3,7 +3,9 @@
 // planning of ghx_cs_exchange_create, then replays every planned unpack segment and every
 // transformed tile record on the host, exactly as k_copy / k_unpack_x index them, with every
 // buffer and field access bounds-checked, and compares each halo cell with the buffer element
-// the reference's unpack reads for it (cubed_sphere/field_descriptor.hpp:81-108). Built with
+// the reference's unpack reads for it (cubed_sphere/field_descriptor.hpp:81-108). Elements of
+// 1, 2, 4, 8 and 16 bytes, both negations (sign-bit flip, two's complement) at 4 and 8 bytes, each
+// at the default tile size and at x_tile_elems 32, 48 and 4096. Built with
 // -fsanitize=address,undefined by tools/cs_host_sanitize.sh; needs no GPU.
 #include <cstdio>
 #include <cstdlib>
@@ -49,7 +51,7 @@ struct field
 
 // a (x, y, z, k) field of one domain with `h` halo cells, memory order by `layout`
 field make_field(const ghx_cs_domain& dom, int c, int levels, int h, const int* layout, int elem,
-                 int nc, int vector)
+                 int nc, int vector, int kind)
 {
     field f{};
     const int shape[4] = {dom.x_last - dom.x_first + 1 + 2 * h, dom.y_last - dom.y_first + 1 + 2 * h,
@@ -72,27 +74,59 @@ field make_field(const ghx_cs_domain& dom, int c, int levels, int h, const int* 
     }
     f.d.num_components = nc;
     f.d.has_components = 1;
-    f.cs = {dom.tile, dom.x_first, dom.y_first, c, vector, elem == 8 ? 1 : 2};
+    f.cs = {dom.tile, dom.x_first, dom.y_first, c, vector, kind};
     f.mem.assign(size_t(stride), 0xC3);
     return f;
 }
 
-// element id stored in the receive buffers: (buffer index << 32) | element index, truncated to
-// the element size
-uint64_t elem_id(size_t buffer, uint64_t index, int elem)
+// an element of up to 16 bytes, little endian: its first `elem` bytes count
+struct value
 {
-    const uint64_t v = (uint64_t(buffer + 1) << 24) ^ index;
-    return elem == 8 ? v : (v & 0xFFFFFFFFu);
+    uint64_t lo = 0, hi = 0;
+    bool operator==(const value& o) const { return lo == o.lo && hi == o.hi; }
+};
+
+value truncated(value v, int elem)
+{
+    if (elem < 16) v.hi = 0;
+    if (elem < 8) v.lo &= (uint64_t(1) << (8 * elem)) - 1;
+    return v;
 }
 
-uint64_t negated(uint64_t v, int elem, int kind)
+// element id stored in the receive buffers: (buffer index << 24) ^ element index, truncated to
+// the element size (4 and 8 bytes); 1- and 2-byte elements hold high bits of its product with an
+// odd constant instead (the id's own low bits would repeat every 256 elements along a row), and
+// a 16-byte element holds that product in its upper half
+value elem_id(size_t buffer, uint64_t index, int elem)
 {
-    if (elem == 8) return kind == 1 ? v ^ (uint64_t(1) << 63) : uint64_t(0) - v;
-    return (kind == 1 ? v ^ 0x80000000u : uint64_t(0) - v) & 0xFFFFFFFFu;
+    value v;
+    v.lo = (uint64_t(buffer + 1) << 24) ^ index;
+    const uint64_t mixed = v.lo * 0x9E3779B97F4A7C15ull;
+    if (elem < 4) v.lo = mixed >> 40;
+    v.hi = mixed | 1;
+    return truncated(v, elem);
 }
 
-void run(const config& cfg, const int* layout, int elem, int nc, int vector)
+// sign-bit flip (kind 1) or two's-complement negation (kind 2) of an element of any width
+value negated(value v, int elem, int kind)
 {
+    if (kind == 1)
+    {
+        if (elem == 16) v.hi ^= uint64_t(1) << 63;
+        else v.lo ^= uint64_t(1) << (8 * elem - 1);
+        return v;
+    }
+    value r;
+    r.lo = uint64_t(0) - v.lo;
+    r.hi = ~v.hi + (v.lo == 0 ? 1 : 0);
+    return truncated(r, elem);
+}
+
+void run(const config& cfg, const int* layout, int elem, int nc, int vector, int kind,
+         int x_tile_elems)
+{
+    // a planning knob: read when the exchange is created
+    if (x_tile_elems) CHECK(ghx_tune("x_tile_elems", x_tile_elems) == GHX_OK);
     std::vector<ghx_cs_domain> doms;
     const int sx = cfg.c / cfg.nx, sy = cfg.c / cfg.ny;
     for (int t = 0; t < 6; ++t)
@@ -110,7 +144,7 @@ void run(const config& cfg, const int* layout, int elem, int nc, int vector)
     std::vector<ghx_cs_item> cs;
     for (size_t a = 0; a < doms.size(); ++a)
     {
-        fields.push_back(make_field(doms[a], cfg.c, cfg.levels, h, layout, elem, nc, vector));
+        fields.push_back(make_field(doms[a], cfg.c, cfg.levels, h, layout, elem, nc, vector, kind));
         ghx_exchange_item it{};
         it.pattern = pat;
         it.local_index = int32_t(a);
@@ -122,6 +156,7 @@ void run(const config& cfg, const int* layout, int elem, int nc, int vector)
     }
     ghx_exchange* ex = nullptr;
     const int rc = ghx_cs_exchange_create(items.data(), cs.data(), int(items.size()), &ex);
+    if (x_tile_elems) CHECK(ghx_tune("reset", 0) == GHX_OK);
     if (rc != GHX_OK) std::printf("create: %s\n", ghx_last_error());
     CHECK(rc == GHX_OK);
     if (!ex)
@@ -137,7 +172,7 @@ void run(const config& cfg, const int* layout, int elem, int nc, int vector)
         CHECK(ex->recv[b].size % uint64_t(elem) == 0);
         for (uint64_t i = 0; i < ex->recv[b].size / uint64_t(elem); ++i)
         {
-            const uint64_t v = elem_id(b, i, elem);
+            const value v = elem_id(b, i, elem);
             std::memcpy(bufs[b].data() + i * elem, &v, size_t(elem));
         }
     }
@@ -185,6 +220,8 @@ void run(const config& cfg, const int* layout, int elem, int nc, int vector)
                 const int bs = g->bmap.empty() ? s.buf_slot : g->bmap[s.buf_slot];
                 const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
                 CHECK(total <= 4096);
+                CHECK(total <= uint32_t(x_tile_elems ? x_tile_elems : 256));
+                CHECK((1 << s.elog2) == elem);
                 uint32_t stored = 0;
                 for (uint32_t i = 0; i < total; ++i)
                 {
@@ -205,7 +242,7 @@ void run(const config& cfg, const int* layout, int elem, int nc, int vector)
                     const bool inside = from + (uint64_t(1) << s.elog2) <= bufs[size_t(bs)].size();
                     CHECK(inside);
                     if (!inside) continue;
-                    uint64_t v = 0;
+                    value v;
                     std::memcpy(&v, bufs[size_t(bs)].data() + from, size_t(1) << s.elog2);
                     const uint32_t comp = s.comp0 + (s.comp_pos < 4 ? cc[s.comp_pos] : 0);
                     if (comp < 2 && ((s.neg_mask >> comp) & 1)) v = negated(v, 1 << s.elog2, s.neg_kind);
@@ -266,12 +303,12 @@ void run(const config& cfg, const int* layout, int elem, int nc, int vector)
                                     CHECK(bc[q] >= 0 && bc[q] < ext[q]);
                                     loc += bc[q] * bstride[q];
                                 }
-                                uint64_t want = elem_id(b, (at + uint64_t(loc)) / uint64_t(elem), elem);
+                                value want = elem_id(b, (at + uint64_t(loc)) / uint64_t(elem), elem);
                                 if (neg) want = negated(want, elem, f.cs.value_kind);
                                 const int64_t off = (x + f.d.offsets[0]) * f.d.byte_strides[0] +
                                                     (y + f.d.offsets[1]) * f.d.byte_strides[1] +
                                                     z * f.d.byte_strides[2] + k * f.d.byte_strides[3];
-                                uint64_t got = 0;
+                                value got;
                                 std::memcpy(&got, f.mem.data() + off, size_t(elem));
                                 CHECK(got == want);
                                 ++cells;
@@ -285,10 +322,14 @@ void run(const config& cfg, const int* layout, int elem, int nc, int vector)
     int32_t nrec = 0, ntiles = 0, nrot = 0;
     uint64_t xbytes = 0;
     CHECK(ghx_cs_plan_info(ex, &nrec, &xbytes, &ntiles, &nrot) == GHX_OK);
-    std::printf("c=%d levels=%d layout=%d%d%d%d elem=%d nc=%d vector=%d: %llu halo cells, %d "
-                "rotated spaces, %d transformed records in %d tiles\n",
-                cfg.c, cfg.levels, layout[0], layout[1], layout[2], layout[3], elem, nc, vector,
-                static_cast<unsigned long long>(cells), nrot, nrec, ntiles);
+    std::printf("c=%d levels=%d layout=%d%d%d%d elem=%d nc=%d vector=%d kind=%d x_tile_elems=%d: "
+                "%llu halo cells, %d rotated spaces, %d transformed records in %d tiles\n",
+                cfg.c, cfg.levels, layout[0], layout[1], layout[2], layout[3], elem, nc, vector, kind,
+                x_tile_elems ? x_tile_elems : 256, static_cast<unsigned long long>(cells), nrot,
+                nrec, ntiles);
+    // every record is covered, by no fewer tiles than its elements need
+    CHECK(uint64_t(ntiles) * uint64_t(x_tile_elems ? x_tile_elems : 256) * uint64_t(elem) >= xbytes);
+    CHECK(ntiles >= nrec);
     ghx_exchange_destroy(ex);
     ghx_pattern_destroy(pat);
 }
@@ -301,11 +342,18 @@ int main()
     const int layouts[][4] = {{3, 2, 1, 0}, {2, 3, 1, 0}, {1, 2, 3, 0}, {0, 1, 2, 3}};
     for (const config& cfg : cfgs)
         for (const auto& layout : layouts)
-        {
-            run(cfg, layout, 8, 1, 0);
-            run(cfg, layout, 4, 3, 1);
-            run(cfg, layout, 8, 2, 1);
-        }
+            for (const int tile : {0, 32, 48, 4096})  // 0: the default, no knob set
+            {
+                run(cfg, layout, 8, 1, 0, 1, tile);
+                run(cfg, layout, 4, 3, 1, 2, tile);
+                run(cfg, layout, 8, 2, 1, 1, tile);
+                // the other widths (scalars: opaque bits), and each width's other negation
+                run(cfg, layout, 1, 1, 0, 0, tile);
+                run(cfg, layout, 2, 3, 0, 0, tile);
+                run(cfg, layout, 16, 1, 0, 0, tile);
+                run(cfg, layout, 8, 3, 1, 2, tile);
+                run(cfg, layout, 4, 2, 1, 1, tile);
+            }
     std::printf(g_fail ? "cs_host_check: %d FAILURES\n" : "cs_host_check: OK\n", g_fail);
     return g_fail ? 1 : 0;
 }

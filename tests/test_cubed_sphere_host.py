@@ -379,3 +379,85 @@ def test_python_module_mirrors_the_generator(ghx):
                 want.setdefault(cs_cases.domain_id(6, cfg["domains"][x[0]]), []).append(b["t"])
         got = {rid: tiles for (rid, _, _, _), tiles in zip(pc.recv_halos(0), pc.halo_tiles(0, 1))}
         assert got == want
+
+
+# ---------------------------------------------------------------------------------------------
+# tile sizes of the transformed unpack
+# ---------------------------------------------------------------------------------------------
+def _fixture_exchange(ghx, cfg, layout, elem, nc, vector, kind):
+    """(pattern, exchange) of one field per domain of a fixture configuration, all on one rank."""
+    pats, _, order = _patterns(ghx, cfg, PLACEMENTS["one_rank"])
+    h = max(cfg["halos"]) + 1
+    items, cs_items = [], []
+    for li, i in enumerate(order):
+        dom = cfg["domains"][i]
+        shape = (dom["x"][1] - dom["x"][0] + 1 + 2 * h, dom["y"][1] - dom["y"][0] + 1 + 2 * h,
+                 cfg["levels"], nc)
+        it = ghx.ExchangeItem()
+        it.pattern, it.local_index, it.kind, it.align, it.tag_offset = pats[0], li, 0, elem, 0
+        fd = it.field
+        fd.dim, fd.elem_size, fd.num_components, fd.has_components = 4, elem, nc, 1
+        stride = elem
+        for d in sorted(range(4), key=lambda d: -layout[d]):
+            fd.byte_strides[d] = stride
+            stride *= shape[d]
+        for d in range(4):
+            fd.layout[d], fd.offsets[d], fd.extents[d] = layout[d], (h if d < 2 else 0), shape[d]
+        cs = ghx.CsItem()
+        cs.tile, cs.first_x, cs.first_y = dom["tile"], dom["x"][0], dom["y"][0]
+        cs.edge_size, cs.is_vector, cs.value_kind = cfg["edge_size"], vector, kind
+        items.append(it)
+        cs_items.append(cs)
+    ex = ctypes.c_void_p()
+    ghx.call("ghx_cs_exchange_create", (ghx.ExchangeItem * len(items))(*items),
+             (ghx.CsItem * len(items))(*cs_items), len(items), ctypes.byref(ex))
+    return pats[0], ex
+
+
+def _rotated_elements(cfg, nc):
+    """Elements of every rotated receive space: the recorded intersections of the boxes whose
+    image turns a step in x into a step in y'."""
+    out = []
+    for dom in cfg["domains"]:
+        for b in dom["boxes"]:
+            if b["t"] != dom["tile"] and b["img"][2] == b["img"][0]:
+                for x in b["x"]:
+                    out.append((x[4] - x[1] + 1) * (x[5] - x[2] + 1) * (x[6] - x[3] + 1) * nc)
+    return out
+
+
+@pytest.mark.parametrize("edge,elem,nc,vector", [(70, 8, 1, 0), (10, 4, 3, 1)])
+def test_x_tile_elems_cuts_the_transformed_records_into_more_or_fewer_tiles(ghx, edge, elem, nc,
+                                                                            vector):
+    """x_tile_elems 32, 48, 256 (the default) and 4096 on the c = 70 scalar f64 field (1,050
+    elements per edge box) and the c = 10 3-vector f32 field (no box above 256 elements): records
+    and bytes do not depend on the knob, the tiles cover every record, and their number falls as
+    the tile grows. The knob is read when the exchange is created."""
+    cfg = cs_cases.config(edge)
+    elements = _rotated_elements(cfg, nc)
+    seen = {}
+    try:
+        for T in (256, 32, 48, 4096):
+            if T != 256:
+                ghx.call("ghx_tune", b"x_tile_elems", T)
+            pat, ex = _fixture_exchange(ghx, cfg, X_FAST, elem, nc, vector, 1)
+            try:
+                n, t, r, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint64()
+                ghx.call("ghx_cs_plan_info", ex, ctypes.byref(n), ctypes.byref(b), ctypes.byref(t),
+                         ctypes.byref(r))
+            finally:
+                ghx.lib().ghx_exchange_destroy(ex)
+                ghx.lib().ghx_pattern_destroy(pat)
+            seen[T] = t.value
+            assert n.value == r.value == len(elements)
+            assert b.value == sum(elements) * elem
+            assert t.value >= sum(-(-e // T) for e in elements), T
+    finally:
+        ghx.call("ghx_tune", b"reset", 0)
+    assert seen[32] > seen[48] > seen[256] >= seen[4096] == len(elements)
+    if edge == 70:
+        assert max(elements) == 1050 and seen[256] > seen[4096]
+    else:  # one tile per record from 256 elements on
+        assert max(elements) <= 256 and seen[256] == seen[4096]
+    for bad in (31, 4097, 0):
+        assert ghx.lib().ghx_tune(b"x_tile_elems", bad) == -1
