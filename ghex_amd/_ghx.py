@@ -99,6 +99,8 @@ _SIGS = {
     "ghx_pattern_key_tiles": (c_i32, [c_vp, c_i32, c_i32, c_i32, P(c_i32), c_i32]),
     "ghx_cs_exchange_create": (c_i32, [P(ExchangeItem), P(CsItem), c_i32, P(c_vp)]),
     "ghx_cs_plan_info": (c_i32, [c_vp, P(c_i32), P(c_u64), P(c_i32), P(c_i32)]),
+    "ghx_cs_self_info": (c_i32, [c_vp, P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
+    "ghx_cs_exchange_self": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
                               c_i32, c_vp]),
     "ghx_udomain_create": (c_i32, [c_i32, P(c_i64), c_i64, P(c_i64), c_i64, P(c_vp)]),

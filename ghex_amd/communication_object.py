@@ -251,7 +251,7 @@ class CommunicationObject:
 
     def __init__(self, context, fuse_self: bool = True, staging=None, pipelined: bool = False,
                  rccl_self: bool = False, max_streams: int = 4, copy_engine: str = "probe",
-                 direct: bool = False, epoch_timeout: float = 30.0):
+                 direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False):
         if staging not in (None, "host"):
             raise ValueError("staging must be None (device buffers) or 'host'")
         if direct and (staging is not None or pipelined or rccl_self):
@@ -272,6 +272,9 @@ class CommunicationObject:
             raise ValueError("rccl_self applies to device buffers only (staging=None)")
         self.context = context
         self.fuse_self = fuse_self
+        # cubed-sphere fields, every message on this rank: pack and rotating unpack in one launch
+        # (ghx_cs_exchange_self). Opt-in; a plan that cannot be fused takes the usual path
+        self.fuse_rotated = bool(fuse_rotated)
         self.staging = staging
         self.pipelined = pipelined
         # tests: route the self messages through RCCL too (a 1-rank communicator), so the
@@ -302,6 +305,15 @@ class CommunicationObject:
             _ghx.call("ghx_exchange_self_fusable", plan.h, ctypes.byref(f))
             plan._all_self = bool(f.value) and all(b["rank"] == me for b in plan.send + plan.recv)
         return plan._all_self
+
+    def cs_self(self, plan) -> bool:
+        """A cubed-sphere exchange whose every message is a self message and which libghx has
+        planned as one launch (ghx_cs_self_info, ghx_cs_exchange_self)."""
+        if getattr(plan, "_cs_self", None) is None:
+            f = ctypes.c_int32()
+            _ghx.call("ghx_cs_self_info", plan.h, ctypes.byref(f), None, None, None)
+            plan._cs_self = bool(f.value)
+        return plan._cs_self
 
     def mixed(self, plan) -> bool:
         """Self AND peer messages: the pack launch also completes the self messages
@@ -489,6 +501,13 @@ class CommunicationObject:
                                               stream.cuda_stream)
             if rc:
                 _ghx.check(rc, "ghx_exchange_self")
+            return CommunicationHandle(self, stream, self._done_event(stream))
+        if self.fuse_self and self.fuse_rotated and self.cs_self(plan):
+            # a whole cube on this rank: pack and rotating unpack in one launch
+            rc = _ghx.lib().ghx_cs_exchange_self(plan.h, fptrs, len(bis), sptrs, len(send),
+                                                 stream.cuda_stream)
+            if rc:
+                _ghx.check(rc, "ghx_cs_exchange_self")
             return CommunicationHandle(self, stream, self._done_event(stream))
         with torch.cuda.stream(stream):
             mixed = self.fuse_self and self.mixed(plan)

@@ -528,6 +528,159 @@ void build_mixed(exchange_plan& ex, int32_t me, const std::vector<ghx_pack_entry
     ex.mixed = true;
 }
 
+// The fused self exchange of a cubed-sphere exchange (cs_self_plan, k_self_cs), built device-less
+// with the exchange; left absent, with the reason in ex.cs_self_reason, when the exchange has a
+// message that leaves the rank, has more pointers than the launch's table, pairs fields of different
+// element size or layout order, or reads a cell it writes. `rhalos`: the halo entry behind each
+// of ex.entries[1].
+void build_cs_self(exchange_plan& ex, const ghx_cs_item* cs, int32_t me,
+                   const std::vector<const halo_entry*>& rhalos)
+{
+    const std::vector<ghx_pack_entry>& sent = ex.entries[0];
+    const std::vector<ghx_pack_entry>& rent = ex.entries[1];
+    auto refuse = [&](const char* why) {
+        ex.cs_self.reset();
+        ex.cs_self_reason = std::string("not fusable: ") + why;
+    };
+    bool self = ex.send.size() == ex.recv.size() && !ex.send.empty();
+    for (size_t i = 0; self && i < ex.send.size(); ++i)
+        self = ex.send[i].first_id == ex.recv[i].first_id && ex.send[i].second_id == ex.recv[i].second_id &&
+               ex.send[i].size == ex.recv[i].size && ex.send[i].rank == me && ex.recv[i].rank == me;
+    if (!self) return refuse("the exchange has peer messages (a recv buffer that is not the send buffer of the same domain pair on this rank)");
+    if (!ex.uentries[0].empty() || !ex.uentries[1].empty() || ex.upack || ex.uunpack)
+        return refuse("the exchange has unstructured items");
+    if (size_t(ex.n_items) + ex.send.size() > size_t(kCsSelfPtrs) || !ex.spack)
+        return refuse("more field and buffer slots than one fused launch's arguments hold (it would need several launch groups)");
+    // the send spaces by the buffer bytes they occupy
+    struct sspace
+    {
+        const ghx_pack_entry* e;
+        const ghx_box* box;
+    };
+    std::map<std::pair<int32_t, uint64_t>, sspace> by_bytes;
+    for (const ghx_pack_entry& e : sent)
+    {
+        uint64_t off = e.buffer_offset;
+        for (int b = 0; b < e.n_boxes; ++b)
+        {
+            by_bytes[{e.buffer_slot, off}] = {&e, &e.boxes[b]};
+            uint64_t n = uint64_t(e.field.num_components) * uint64_t(e.field.elem_size);
+            for (int d = 0; d < 3; ++d) n *= uint64_t(int64_t(e.boxes[b].last[d]) - e.boxes[b].first[d] + 1);
+            off += n;
+        }
+    }
+    // Source check: every source box lies in its field's own domain cells — at or above local
+    // cell 0 in x and y, and clear of every box the exchange writes into that field (the domain's
+    // upper corner is not part of a cubed-sphere item; the receive boxes are what must be missed).
+    // No cell the launch reads is then a cell it writes.
+    for (const ghx_pack_entry& e : sent)
+        for (int b = 0; b < e.n_boxes; ++b)
+        {
+            const ghx_box& s = e.boxes[b];
+            if (s.first[0] < 0 || s.first[1] < 0 || s.first[2] < 0)
+                return refuse("a source box reaches into its field's halo");
+            for (size_t k = 0; k < rent.size(); ++k)
+            {
+                if (rent[k].field_slot != e.field_slot) continue;
+                for (const is_pair& w : rhalos[k]->boxes)
+                {
+                    bool meet = true;
+                    for (int d = 0; d < 3; ++d) meet = meet && s.first[d] <= w.ll[d] && w.lf[d] <= s.last[d];
+                    if (meet) return refuse("a source box reaches into its field's halo (cells the exchange writes)");
+                }
+            }
+        }
+    std::vector<seg_s> pack, unpack;
+    std::vector<int32_t> gf_p, gf_u, gb;
+    std::vector<xsbox> boxes;
+    for (size_t k = 0; k < rent.size(); ++k)
+    {
+        const ghx_pack_entry& re = rent[k];
+        const halo_entry& he = *rhalos[k];
+        const ghx_field_desc& fr = re.field;
+        uint64_t off = re.buffer_offset;
+        for (size_t b = 0; b < he.boxes.size(); ++b)
+        {
+            const auto it = by_bytes.find({re.buffer_slot, off});
+            if (it == by_bytes.end())
+                return refuse("a receive space has no send space at the same buffer bytes");
+            const ghx_pack_entry& se = *it->second.e;
+            const ghx_box& sbox = *it->second.box;
+            const ghx_field_desc& fs = se.field;
+            bool same = fs.elem_size == fr.elem_size && fs.dim == fr.dim &&
+                        fs.has_components == fr.has_components && fs.num_components == fr.num_components;
+            for (int d = 0; same && d < fr.dim; ++d) same = fs.layout[d] == fr.layout[d];
+            if (!same)
+                return refuse("paired fields differ in element size, components or layout order "
+                              "(the buffer's axis order differs between the two sides)");
+            cs_recv_plan rp;
+            uint64_t nb = 0;
+            cs_plan_space(rp, fr, cs[re.field_slot], he.boxes[b], he.tiles[b], re.field_slot,
+                          re.buffer_slot, off, &nb);
+            bool paired = rp.xs.empty();
+            std::vector<seg_s> ps;
+            if (paired)
+            {
+                add_box_segments(ps, fs, sbox, 0, 0, off);
+                paired = ps.size() == rp.segs.size();
+                for (size_t i = 0; paired && i < ps.size(); ++i)
+                    paired = exchange_plan::same_message(ps[i], rp.segs[i]);
+            }
+            if (paired)
+            {
+                for (size_t i = 0; i < ps.size(); ++i)
+                {
+                    pack.push_back(ps[i]);
+                    unpack.push_back(rp.segs[i]);
+                    gf_p.push_back(se.field_slot);
+                    gf_u.push_back(re.field_slot);
+                    gb.push_back(re.buffer_slot);
+                }
+            }
+            else
+            {
+                const int64_t elem = fr.elem_size;
+                if (elem > 16 || (elem & (elem - 1)))
+                    return refuse("a space that cannot be paired holds elements that are not 1, 2, 4, 8 or 16 bytes");
+                xsbox x{};
+                x.dst = rp.xs.empty() ? cs_space_box(fr, cs[re.field_slot], he.boxes[b], he.tiles[b],
+                                                     re.field_slot, re.buffer_slot, off)
+                                      : rp.xs[0];
+                // the sending side of the same dense box: its axes are the sender's dims in
+                // layout order, fastest first — the receiver's order, the layouts being equal
+                const int D = fs.dim;
+                int by_speed[GHX_MAX_DIM];
+                for (int d = 0; d < D; ++d) by_speed[D - 1 - fs.layout[d]] = d;
+                x.src_off = 0;
+                for (int d = 0; d < 3; ++d)
+                    x.src_off += (int64_t(sbox.first[d]) + fs.offsets[d]) * fs.byte_strides[d];
+                for (int a = 0; a < 4; ++a) x.src_stride[a] = 0;
+                for (int a = 0; a < D; ++a)
+                {
+                    const int d = by_speed[a];
+                    const int64_t ext = d < 3 ? int64_t(sbox.last[d]) - sbox.first[d] + 1
+                                              : int64_t(fs.num_components);
+                    if (ext != int64_t(x.dst.ext[a]))
+                        return refuse("a send space and its receive space differ in shape");
+                    x.src_stride[a] = fs.byte_strides[d];
+                }
+                x.src_slot = se.field_slot;
+                boxes.push_back(x);
+            }
+            off += nb;
+        }
+    }
+    try
+    {
+        ex.cs_self = std::make_unique<cs_self_plan>(pack, unpack, gf_p, gf_u, gb, boxes);
+        ex.cs_self_reason.clear();
+    }
+    catch (const invalid& e)
+    {
+        refuse(e.what());
+    }
+}
+
 int check_ptr(const void* p, const char* what)
 {
     if (!p) throw invalid(std::string("null argument: ") + what);
@@ -1172,6 +1325,7 @@ static int make_exchange(const ghx_exchange_item* items, const ghx_cs_item* cs, 
     auto ex = std::make_unique<ghx_exchange>();
     ex->n_items = n_items;
     std::vector<ghx_pack_entry> rent;              // receive entries, for build_mixed
+    std::vector<const halo_entry*> rhalos;         // and their halo entries, for build_cs_self
     for (int dir = 0; dir < 2; ++dir)
     {
         const bool receive = dir == 1;
@@ -1188,6 +1342,7 @@ static int make_exchange(const ghx_exchange_item* items, const ghx_cs_item* cs, 
         ex->entries[dir] = sent;
         ex->uentries[dir] = uent;
         if (receive) rent = sent;
+        if (receive) rhalos = halos;
         if (receive && cs)
         {
             cs_recv_plan rp;
@@ -1249,6 +1404,8 @@ static int make_exchange(const ghx_exchange_item* items, const ghx_cs_item* cs, 
         upload_pair_records(ex->self_recs, p.host_segs, q.host_segs, p.host_tiles);
     }
     if (ex->cs_rotated == 0) build_mixed(*ex, items[0].pattern->my_rank, rent);
+    if (cs) build_cs_self(*ex, cs, items[0].pattern->my_rank, rhalos);
+    else ex->cs_self_reason = "not fusable: not a cubed-sphere exchange";
     *out = ex.release();
     return GHX_OK;
 }
@@ -1287,6 +1444,37 @@ int ghx_cs_plan_info(const ghx_exchange* ex, int32_t* n_records, uint64_t* bytes
         if (n_tiles) *n_tiles = ex->xunpack ? int32_t(ex->xunpack->n_tiles) : 0;
         if (n_rotated) *n_rotated = ex->cs_rotated;
         return GHX_OK;
+    });
+}
+
+int ghx_cs_self_info(const ghx_exchange* ex, int32_t* fusable, int32_t* n_pair_tiles,
+                     int32_t* n_x_records, int32_t* n_x_tiles)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(fusable, "fusable");
+        const cs_self_plan* p = ex->cs_self.get();
+        *fusable = p ? 1 : 0;
+        if (n_pair_tiles) *n_pair_tiles = p ? int32_t(p->n_pair_tiles()) : 0;
+        if (n_x_records) *n_x_records = p ? p->n_x_records : 0;
+        if (n_x_tiles) *n_x_tiles = p ? int32_t(p->n_x_tiles()) : 0;
+        if (!p) set_error(ex->cs_self_reason);
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_exchange_self(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                         void* const* buffers, int32_t n_buffers, ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        if (!ex->cs_self) throw invalid("cubed-sphere self exchange: " + ex->cs_self_reason);
+        if (ex->dir_parity[0].word)
+            throw invalid("cubed-sphere self exchange: the send side has double-buffered buffers "
+                          "(ghx_exchange_set_parity); the fused launch writes one copy");
+        check_ptr(field_ptrs, "field_ptrs");
+        check_ptr(buffers, "buffers");
+        return ex->cs_self->execute(field_ptrs, n_fields, buffers, n_buffers, stream);
     });
 }
 

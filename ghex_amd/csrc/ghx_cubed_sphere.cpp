@@ -423,4 +423,75 @@ void cs_plan_space(cs_recv_plan& out, const ghx_field_desc& f, const ghx_cs_item
     out.sbytes += *space_bytes;
 }
 
+// The receiving side of ANY space cs_plan_space has accepted, as a transformed box: per axis of
+// the buffer's dense box the extent and the signed field byte stride, the field offset of buffer
+// cell 0 and the components to negate. For the spaces cs_plan_space itself transforms this is
+// the box it makes; own-tile and translation-only spaces have the field's own strides.
+xseg cs_space_box(const ghx_field_desc& f, const ghx_cs_item& cs, const is_pair& sp, int32_t gtile,
+                  int32_t field_slot, int32_t buf_slot, uint64_t buf_off)
+{
+    const int D = f.dim;
+    const int64_t elem = f.elem_size;
+    if (elem < 1 || elem > 16 || (elem & (elem - 1)))
+        throw invalid("a self tile record needs an element size of 1, 2, 4, 8 or 16 bytes");
+    int r[4] = {1, 0, 0, 1};
+    int32_t p0[2] = {sp.lf[0], sp.lf[1]};  // the field cell of the global box's first cell
+    uint8_t neg = 0;
+    if (gtile != cs.tile)
+    {
+        const int n = cs_neighbour_index(cs.tile, gtile);
+        if (n < 0) throw invalid("iteration space from a tile that is no edge neighbour of the field's tile");
+        const cs_transform& t = cs_transform_of(cs.tile, n);
+        if (t.switched_xy())
+        {
+            for (int k = 0; k < 4; ++k) r[k] = t.r[k];
+            t.invert(sp.gf[0], sp.gf[1], cs.edge_size, p0);
+            p0[0] -= cs.first_x;
+            p0[1] -= cs.first_y;
+            if (cs.is_vector)
+            {
+                if (t.r[2] == -1) neg |= 1;
+                if (t.r[1] == -1 && f.num_components > 1) neg |= 2;
+            }
+        }
+    }
+    const int64_t sx = f.byte_strides[0], sy = f.byte_strides[1];
+    int64_t bext[GHX_MAX_DIM] = {1, 1, 1, 1}, bstr[GHX_MAX_DIM] = {0, 0, 0, 0};
+    for (int k = 0; k < 3; ++k) bext[k] = int64_t(sp.gl[k]) - sp.gf[k] + 1;
+    bstr[0] = r[0] * sx + r[1] * sy;
+    bstr[1] = r[2] * sx + r[3] * sy;
+    bstr[2] = f.byte_strides[2];
+    if (f.has_components)
+    {
+        bext[3] = f.num_components;
+        bstr[3] = f.byte_strides[3];
+    }
+    int by_speed[GHX_MAX_DIM];
+    for (int d = 0; d < D; ++d) by_speed[D - 1 - f.layout[d]] = d;
+    xseg b{};
+    b.field_off = (int64_t(p0[0]) + f.offsets[0]) * sx + (int64_t(p0[1]) + f.offsets[1]) * sy +
+                  (int64_t(sp.lf[2]) + f.offsets[2]) * f.byte_strides[2];
+    b.buf_off = buf_off;
+    b.comp_axis = -1;
+    for (int k = 0; k < 4; ++k)
+    {
+        b.ext[k] = 1;
+        b.stride[k] = 0;
+    }
+    for (int k = 0; k < D; ++k)
+    {
+        b.ext[k] = uint32_t(bext[by_speed[k]]);
+        b.stride[k] = bstr[by_speed[k]];
+        if (f.has_components && by_speed[k] == D - 1) b.comp_axis = k;
+    }
+    b.elem = uint32_t(elem);
+    b.neg_mask = neg;
+    b.neg_kind = uint8_t(cs.value_kind);
+    b.field_slot = field_slot;
+    b.buf_slot = buf_slot;
+    b.tile_elems = g_tune.x_tile_elems;
+    if (b.bytes() >= (uint64_t(1) << 31) - kMaxTileBytes) throw invalid("rotated iteration space of 2 GiB or more");
+    return b;
+}
+
 }  // namespace ghx

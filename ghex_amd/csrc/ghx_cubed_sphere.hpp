@@ -57,4 +57,8 @@ void check_cs_item(const ghx_field_desc& f, const ghx_cs_item& cs);
 void cs_plan_space(cs_recv_plan& out, const ghx_field_desc& f, const ghx_cs_item& cs,
                    const is_pair& sp, int32_t gtile, int32_t field_slot, int32_t buf_slot,
                    uint64_t buf_off, uint64_t* space_bytes);
+// The receiving side of a space cs_plan_space has accepted, as a transformed box whatever form
+// cs_plan_space gave it (the fused self exchange's tile records; element sizes 1..16, powers of 2)
+xseg cs_space_box(const ghx_field_desc& f, const ghx_cs_item& cs, const is_pair& sp, int32_t gtile,
+                  int32_t field_slot, int32_t buf_slot, uint64_t buf_off);
 }  // namespace ghx

@@ -57,6 +57,10 @@ struct exchange_plan
     // which know nothing of the rotation.
     std::unique_ptr<xplan> xunpack;
     int32_t cs_rotated = 0;
+    // the fused self exchange of a cubed-sphere exchange whose every message stays on this rank
+    // (ghx_cs_exchange_self): null when it cannot be fused, cs_self_reason then says why
+    std::unique_ptr<cs_self_plan> cs_self;
+    std::string cs_self_reason;
 
     void make_split()
     {

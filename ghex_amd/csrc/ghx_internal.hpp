@@ -199,6 +199,23 @@ struct alignas(16) seg_x
 };
 static_assert(sizeof(seg_x) == 144, "seg_x layout");
 
+// Self tile record (fused cubed-sphere self exchange): a seg_x tile of the
+// RECEIVING field plus the SENDING side of the same buffer cells. The buffer box is the sender's
+// dense box in the sender's own coordinates, so the source address is affine in the tile
+// coordinates as the destination's is: src_off + sum c_k * src_stride[k], the axes those of `x`.
+// k_self_cs loads the element from the source field, stores it unmodified to the buffer cell and,
+// negated as `x` says, to the destination field.
+struct alignas(16) seg_xs
+{
+    seg_x x;                // destination tile (x.field_slot, x.field_off, x.stride) and buffer side
+    int64_t src_off;        // source field byte offset of the tile's first cell
+    int64_t src_stride[4];  // signed source field byte stride per tile axis
+    uint16_t src_slot;      // field slot of the sending field
+    uint8_t pad[6];
+};
+static_assert(sizeof(seg_xs) == 192, "seg_xs layout");
+static_assert(alignof(seg_xs) == 16, "seg_xs alignment");
+
 // Kernel arguments (passed by value: <= 1.7 KB of kernarg).
 struct kargs
 {
@@ -213,6 +230,25 @@ struct kargs
     uint64_t buf_ptr[GHX_MAX_SLOTS];
     int64_t dbl_off[GHX_MAX_SLOTS];  // per buffer slot: byte offset of its odd-parity copy (0: none)
 };
+
+// Arguments of the fused cubed-sphere self exchange (k_self_cs): blocks [0, n_pair_tiles) take
+// the pair record (two seg_s, as k_self's) at their index, the next n_x_tiles a seg_xs record.
+// One pointer array holds the field pointers (slot s at ptr[s]) and after them the buffer
+// pointers (slot b at ptr[buf_base + b]): a whole cube on one rank has few fields and many
+// domain-pair buffers (24 domains: 168), more than kargs' GHX_MAX_SLOTS of each, and the launch
+// is only worth having if it is ONE launch. 3.6 KB of kernarg.
+constexpr int kCsSelfPtrs = 448;
+struct kargs_cs
+{
+    const void* pair_recs;
+    const void* x_recs;
+    uint32_t n_pair_tiles;
+    uint32_t n_x_tiles;
+    uint32_t buf_base;
+    uint32_t pad;
+    uint64_t ptr[kCsSelfPtrs];
+};
+static_assert(sizeof(kargs_cs) < 4096, "kargs_cs is passed by value");
 
 // Double-buffered buffers (the direct exchange's one-launch epochs, ghx_epochs.hip): a buffer
 // exists twice, its odd-parity copy `offset` bytes after the even one, and a launch uses the copy
@@ -248,6 +284,7 @@ int launch_unstructured(const kargs& a, int direction, void* stream, uint32_t gr
 int launch_self(const kargs& a, void* stream, uint32_t grid);
 int launch_put(const kargs& a, void* stream, uint32_t grid);
 int launch_unpack_x(const kargs& a, void* stream, uint32_t grid);  // tile_recs: seg_x records
+int launch_self_cs(const kargs_cs& a, void* stream, uint32_t grid);
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

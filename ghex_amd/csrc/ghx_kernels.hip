@@ -1019,6 +1019,156 @@ __global__ __launch_bounds__(kBlock) void k_unpack_x(kargs a)
     }
 }
 
+// Fused cubed-sphere self exchange: pack and rotating unpack of an exchange
+// whose every message stays on this device, in ONE launch. Blocks [0, n_pair_tiles) take a pair
+// record and do what k_self's record form does with it (spaces whose pack and unpack segments
+// cover the same bytes with the same rows); the blocks after them take a self tile record
+// (seg_xs): each lane loads ONE element from the sending field, stores it as it is to its cell of
+// the buffer's dense box (the send buffers hold the packed message afterwards) and, negated in
+// registers as unpack_x_tile negates, to the receiving field. No buffer read-back, no LDS. The
+// planner has checked that no cell the launch reads is a cell it writes, so workgroups need no
+// ordering among themselves.
+template<int E>
+__device__ __forceinline__ void self_x_tile(const seg_xs& r, const char* __restrict__ src,
+                                            char* __restrict__ buf, char* __restrict__ field,
+                                            bool aligned)
+{
+    using V = typename vec_t<(1 << E)>::type;
+    const seg_x& s = r.x;
+    const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
+    for (uint32_t i = threadIdx.x; i < total; i += kBlock)
+    {
+        const uint32_t q0 = fastdiv(i, s.mag[0]);
+        const uint32_t c0 = i - q0 * s.tdim[0];
+        const uint32_t q1 = fastdiv(q0, s.mag[1]);
+        const uint32_t c1 = q0 - q1 * s.tdim[1];
+        const uint32_t c3 = fastdiv(q1, s.mag[2]);
+        const uint32_t c2 = q1 - c3 * s.tdim[2];
+        if (c0 >= s.act[0] || c1 >= s.act[1] || c2 >= s.act[2] || c3 >= s.act[3]) continue;
+        const char* from = src + r.src_off + int64_t(c0) * r.src_stride[0] +
+                           int64_t(c1) * r.src_stride[1] + int64_t(c2) * r.src_stride[2] +
+                           int64_t(c3) * r.src_stride[3];
+        const uint32_t bi = c0 * s.bstride[0] + c1 * s.bstride[1] + c2 * s.bstride[2] +
+                            c3 * s.bstride[3];
+        char* cell = buf + (size_t(bi) << E);
+        V v;
+        if (aligned)
+        {
+            v = vload<V>(from);
+            vstore<V>(cell, v);
+        }
+        else
+        {
+            // a field or buffer whose base or strides are not multiples of the element size
+            unsigned char b[1 << E];
+#pragma unroll
+            for (int k = 0; k < (1 << E); ++k) b[k] = vload<unsigned char>(from + k);
+#pragma unroll
+            for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(cell + k, b[k]);
+            __builtin_memcpy(&v, b, sizeof(V));
+        }
+        if (s.neg_mask)
+        {
+            uint32_t comp = s.comp0;
+            if (s.comp_pos < 4) comp += s.comp_pos == 0 ? c0 : s.comp_pos == 1 ? c1 : s.comp_pos == 2 ? c2 : c3;
+            if (comp < 2 && ((s.neg_mask >> comp) & 1u))
+            {
+                if constexpr (E == 2)
+                    v = s.neg_kind == 1 ? (v ^ 0x80000000u) : (0u - v);
+                else if constexpr (E == 3)
+                {
+                    if (s.neg_kind == 1) v.y ^= 0x80000000u;
+                    else
+                    {
+                        const uint64_t w = 0ull - ((uint64_t(v.y) << 32) | v.x);
+                        v.x = uint32_t(w);
+                        v.y = uint32_t(w >> 32);
+                    }
+                }
+            }
+        }
+        char* dst = field + s.field_off + int64_t(c0) * s.stride[0] + int64_t(c1) * s.stride[1] +
+                    int64_t(c2) * s.stride[2] + int64_t(c3) * s.stride[3];
+        if (aligned) vstore<V>(dst, v);
+        else
+        {
+            unsigned char b[1 << E];
+            __builtin_memcpy(b, &v, sizeof(V));
+#pragma unroll
+            for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(dst + k, b[k]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_self_cs(kargs_cs a)
+{
+    const seg_s* __restrict__ pairs = static_cast<const seg_s*>(a.pair_recs);
+    const seg_xs* __restrict__ xrecs = static_cast<const seg_xs*>(a.x_recs);
+    const uint32_t n_tiles = a.n_pair_tiles + a.n_x_tiles;
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x)
+    {
+        if (t < a.n_pair_tiles)  // uniform per workgroup
+        {
+            const seg_s s = pairs[2 * t];
+            const seg_s q = pairs[2 * t + 1];
+            const uint32_t start = s.first_tile * s.tile_bytes;
+            const uint32_t end = min(start + s.tile_bytes, s.bytes);
+            char* field_p = reinterpret_cast<char*>(a.ptr[s.field_slot]);
+            char* field_u = reinterpret_cast<char*>(a.ptr[q.field_slot]);
+            char* buf = reinterpret_cast<char*>(a.ptr[a.buf_base + s.buf_slot]) + s.buf_off;
+            int wp = min(int(s.wlog2), ptr_wlog2(reinterpret_cast<uint64_t>(field_p)));
+            wp = min(wp, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
+            int wu = min(int(q.wlog2), ptr_wlog2(reinterpret_cast<uint64_t>(field_u)));
+            wu = min(wu, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
+            if (wp == wu && s.amode == 1 && q.amode == 1 && wp >= 3)
+            {
+                if (wp == 4) self_forward<16, 1>(s, q, field_p, field_u, buf, start, end);
+                else self_forward<8, 1>(s, q, field_p, field_u, buf, start, end);
+                continue;
+            }
+            if (wp == wu)
+            {
+                switch (wp)
+                {
+                    case 4: self_forward<16>(s, q, field_p, field_u, buf, start, end); break;
+                    case 3: self_forward<8>(s, q, field_p, field_u, buf, start, end); break;
+                    case 2: self_forward<4>(s, q, field_p, field_u, buf, start, end); break;
+                    case 1: self_forward<2>(s, q, field_p, field_u, buf, start, end); break;
+                    default: self_forward<1>(s, q, field_p, field_u, buf, start, end); break;
+                }
+                continue;
+            }
+            copy_any<true, kU>(s, field_p, buf, start, end, wp);
+            __syncthreads();  // workgroup release/acquire: the tile's buffer bytes are complete
+            copy_any<false, kU>(q, field_u, buf, start, end, wu);
+            __syncthreads();  // the next tile of a grid-stride loop reuses the lanes
+            continue;
+        }
+        const seg_xs r = xrecs[t - a.n_pair_tiles];
+        const char* src = reinterpret_cast<const char*>(a.ptr[r.src_slot]);
+        char* buf = reinterpret_cast<char*>(a.ptr[a.buf_base + r.x.buf_slot]) + r.x.buf_off;
+        char* field = reinterpret_cast<char*>(a.ptr[r.x.field_slot]);
+        // element-wide accesses when the source, the buffer, the destination and every stride
+        // are element-aligned (uniform per tile)
+        const uint64_t em = (1u << r.x.elog2) - 1u;
+        const bool aligned =
+            ((reinterpret_cast<uint64_t>(src) + uint64_t(r.src_off)) & em) == 0 &&
+            (reinterpret_cast<uint64_t>(buf) & em) == 0 &&
+            ((reinterpret_cast<uint64_t>(field) + uint64_t(r.x.field_off)) & em) == 0 &&
+            ((uint64_t(r.x.stride[0]) | uint64_t(r.x.stride[1]) | uint64_t(r.x.stride[2]) |
+              uint64_t(r.x.stride[3]) | uint64_t(r.src_stride[0]) | uint64_t(r.src_stride[1]) |
+              uint64_t(r.src_stride[2]) | uint64_t(r.src_stride[3])) & em) == 0;
+        switch (r.x.elog2)
+        {
+            case 4: self_x_tile<4>(r, src, buf, field, aligned); break;
+            case 3: self_x_tile<3>(r, src, buf, field, aligned); break;
+            case 2: self_x_tile<2>(r, src, buf, field, aligned); break;
+            case 1: self_x_tile<1>(r, src, buf, field, aligned); break;
+            default: self_x_tile<0>(r, src, buf, field, aligned); break;
+        }
+    }
+}
+
 int launched(const char* what)
 {
     const hipError_t e = hipGetLastError();
@@ -1130,6 +1280,14 @@ int launch_unpack_x(const kargs& a, void* stream, uint32_t grid)
     if (a.n_tiles == 0) return GHX_OK;
     launch(k_unpack_x, min(grid, a.n_tiles), static_cast<hipStream_t>(stream), a);
     return launched("transformed unpack");
+}
+
+int launch_self_cs(const kargs_cs& a, void* stream, uint32_t grid)
+{
+    const uint32_t n_tiles = a.n_pair_tiles + a.n_x_tiles;
+    if (n_tiles == 0) return GHX_OK;
+    launch(k_self_cs, min(grid, n_tiles), static_cast<hipStream_t>(stream), a);
+    return launched("cubed-sphere self-exchange");
 }
 
 template<bool DBL, bool REC>

@@ -631,7 +631,7 @@ void finish_segment(seg_s& s)
 // the axes are filled in buffer order. The store side walks the tile with its axes sorted by
 // ascending |field stride| (axes of extent 1 last).
 void make_tile_records(std::vector<seg_x>& out, const xseg& b, uint16_t field_slot,
-                       uint16_t buf_slot)
+                       uint16_t buf_slot, std::vector<xtile_pos>* where)
 {
     if (b.elem < 1 || b.elem > 16 || (b.elem & (b.elem - 1))) throw invalid("transformed segment: element size");
     if (b.bytes() == 0 || b.bytes() >= (uint64_t(1) << 31)) throw invalid("transformed segment: box size");
@@ -704,6 +704,16 @@ void make_tile_records(std::vector<seg_x>& out, const xseg& b, uint16_t field_sl
                     r.neg_mask = b.neg_mask;
                     r.neg_kind = b.neg_kind;
                     out.push_back(r);
+                    if (where)
+                    {
+                        xtile_pos w{};
+                        for (int k = 0; k < 4; ++k)
+                        {
+                            w.origin[k] = o[k];
+                            w.axis[k] = perm[k];
+                        }
+                        where->push_back(w);
+                    }
                 }
 }
 
@@ -758,6 +768,113 @@ int xplan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* s
         rc = launch_unpack_x(a, stream, grid_for_tiles(a.n_tiles));
     }
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// fused cubed-sphere self exchange
+// ---------------------------------------------------------------------------------------------
+cs_self_plan::cs_self_plan(const std::vector<seg_s>& pack, const std::vector<seg_s>& unpack,
+                           const std::vector<int32_t>& gf_p, const std::vector<int32_t>& gf_u,
+                           const std::vector<int32_t>& gb, const std::vector<xsbox>& boxes)
+{
+    if (pack.size() != unpack.size() || gf_p.size() != pack.size() || gf_u.size() != pack.size() ||
+        gb.size() != pack.size())
+        throw invalid("self plan: one unpack segment and one slot triple per pack segment");
+    auto slot = [&](int32_t f, int32_t b) {
+        if (f < 0 || b < 0) throw invalid("negative slot");
+        max_field_slot = std::max(max_field_slot, f);
+        max_buf_slot = std::max(max_buf_slot, b);
+        if (max_field_slot + 1 + max_buf_slot + 1 > kCsSelfPtrs)
+            throw invalid("more field and buffer slots than the fused launch's arguments hold");
+    };
+    if (!pack.empty())
+    {
+        std::vector<seg_s> p = pack, q = unpack;
+        for (size_t k = 0; k < pack.size(); ++k)
+        {
+            slot(gf_p[k], gb[k]);
+            slot(gf_u[k], gb[k]);
+            p[k].field_slot = uint16_t(gf_p[k]);
+            q[k].field_slot = uint16_t(gf_u[k]);
+            p[k].buf_slot = q[k].buf_slot = uint16_t(gb[k]);
+        }
+        // tile sizes, cache policies and the dispatch order are the ordinary plans' (build_tiles),
+        // with the fused self exchange's tile size as ghx_exchange_self uses it; the launch is
+        // tiled by the pack side's table alone, as k_self is
+        const uint32_t saved = g_tune.tile_bytes;
+        g_tune.tile_bytes = g_tune.self_tile_bytes;
+        const std::vector<uint32_t> tiles = build_tiles(p, 0);
+        (void)build_tiles(q, 1);
+        g_tune.tile_bytes = saved;
+        pair_recs.resize(tiles.size());  // 2 per tile
+        for (size_t t = 0; t < tiles.size() / 2; ++t)
+        {
+            const uint32_t si = tiles[2 * t];
+            pair_recs[2 * t] = p[si];
+            pair_recs[2 * t].first_tile = tiles[2 * t + 1];
+            pair_recs[2 * t + 1] = q[si];
+        }
+    }
+    for (const xsbox& b : boxes)
+    {
+        slot(b.dst.field_slot, b.dst.buf_slot);
+        slot(b.src_slot, b.dst.buf_slot);
+        std::vector<seg_x> recs;
+        std::vector<xtile_pos> where;
+        make_tile_records(recs, b.dst, uint16_t(b.dst.field_slot), uint16_t(b.dst.buf_slot), &where);
+        for (size_t t = 0; t < recs.size(); ++t)
+        {
+            seg_xs r{};
+            r.x = recs[t];
+            r.src_off = b.src_off;
+            for (int k = 0; k < 4; ++k) r.src_off += int64_t(where[t].origin[k]) * b.src_stride[k];
+            for (int j = 0; j < 4; ++j) r.src_stride[j] = b.src_stride[where[t].axis[j]];
+            r.src_slot = uint16_t(b.src_slot);
+            x_recs.push_back(r);
+        }
+        ++n_x_records;
+    }
+    if (!have_device()) return;
+    if (!pair_recs.empty())
+    {
+        const size_t nb = pair_recs.size() * sizeof(seg_s);
+        if (hipMalloc(&dev.segs, nb) != hipSuccess) throw hip_error("hipMalloc(self pair records)");
+        if (hipMemcpy(dev.segs, pair_recs.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
+            throw hip_error("hipMemcpy(self pair records)");
+    }
+    if (!x_recs.empty())
+    {
+        const size_t nb = x_recs.size() * sizeof(seg_xs);
+        if (hipMalloc(&dev.recs, nb) != hipSuccess) throw hip_error("hipMalloc(self tile records)");
+        if (hipMemcpy(dev.recs, x_recs.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
+            throw hip_error("hipMemcpy(self tile records)");
+    }
+}
+
+int cs_self_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
+{
+    const uint32_t nt = n_pair_tiles() + n_x_tiles();
+    if (nt == 0) return GHX_OK;
+    if (nf <= max_field_slot || nb <= max_buf_slot) throw invalid("pointer arrays do not cover the plan's slots");
+    if ((!pair_recs.empty() && !dev.segs) || (!x_recs.empty() && !dev.recs))
+        throw hip_error("plan has no device tables (no HIP device at creation)");
+    kargs_cs a{};
+    a.pair_recs = dev.segs;
+    a.x_recs = dev.recs;
+    a.n_pair_tiles = n_pair_tiles();
+    a.n_x_tiles = n_x_tiles();
+    a.buf_base = uint32_t(max_field_slot + 1);
+    for (int i = 0; i <= max_field_slot; ++i)
+    {
+        if (!fptr[i]) throw invalid("null field pointer");
+        a.ptr[i] = reinterpret_cast<uint64_t>(fptr[i]);
+    }
+    for (int i = 0; i <= max_buf_slot; ++i)
+    {
+        if (!bptr[i]) throw invalid("null buffer pointer");
+        a.ptr[a.buf_base + uint32_t(i)] = reinterpret_cast<uint64_t>(bptr[i]);
+    }
+    return launch_self_cs(a, stream, grid_for_tiles(nt));
 }
 
 // ---------------------------------------------------------------------------------------------

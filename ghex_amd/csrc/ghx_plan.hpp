@@ -110,9 +110,47 @@ struct xplan
     explicit xplan(std::vector<xseg> boxes);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
-// the tile records of one box (local slots as given)
+// where a tile record lies in its box: the tile's origin per BUFFER axis of the xseg, and the
+// buffer axis each of the record's (stride-sorted) axes is
+struct xtile_pos
+{
+    uint32_t origin[4];
+    int32_t axis[4];
+};
+// the tile records of one box (local slots as given); `where`, if given, gains one entry per record
 void make_tile_records(std::vector<seg_x>& out, const xseg& b, uint16_t field_slot,
-                       uint16_t buf_slot);
+                       uint16_t buf_slot, std::vector<xtile_pos>* where = nullptr);
+
+// Fused cubed-sphere self exchange (k_self_cs): every message of the exchange is
+// a self message, so ONE launch reads each sent cell from the sending field and writes it to the
+// send buffer and to the receiving field's halo. Receive spaces whose unpack segments cover the
+// same bytes with the same rows as the pack segments become pair records (as k_self's); every
+// other space becomes self tile records (seg_xs). Built without a device; the records are kept on
+// the host for inspection and uploaded when there is a device.
+struct xsbox
+{
+    xseg dst;               // the receiving side (slots: the receiving field's, the buffer's)
+    int64_t src_off;        // sending field: byte offset of buffer cell (0, 0, 0, 0)
+    int64_t src_stride[4];  // and its byte stride per buffer axis
+    int32_t src_slot;
+};
+struct cs_self_plan
+{
+    std::vector<seg_s> pair_recs;  // two per pair tile: the pack segment (first_tile = the tile's
+                                   // index in it), then the unpack segment
+    std::vector<seg_xs> x_recs;    // one per self tile
+    int32_t n_x_records = 0;       // spaces (boxes) behind x_recs
+    int max_field_slot = -1, max_buf_slot = -1;
+    device_tables dev;             // dev.segs: pair_recs, dev.recs: x_recs
+    uint32_t n_pair_tiles() const { return uint32_t(pair_recs.size() / 2); }
+    uint32_t n_x_tiles() const { return uint32_t(x_recs.size()); }
+    // pack / unpack segments of the paired spaces (segment k of each over the same bytes, caller
+    // slots gf_p / gf_u / gb) and the boxes of the others
+    cs_self_plan(const std::vector<seg_s>& pack, const std::vector<seg_s>& unpack,
+                 const std::vector<int32_t>& gf_p, const std::vector<int32_t>& gf_u,
+                 const std::vector<int32_t>& gb, const std::vector<xsbox>& boxes);
+    int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
+};
 
 // unstructured fused plan
 struct uplan

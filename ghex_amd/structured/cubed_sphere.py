@@ -19,8 +19,12 @@ from ..pattern import PatternContainer
 from .regular import _layout_order
 
 
-def make_communication_object(context, **options) -> CommunicationObject:
-    return CommunicationObject(context, **options)
+def make_communication_object(context, fuse_rotated: bool = False,
+                              **options) -> CommunicationObject:
+    """The plain communication object. fuse_rotated=True (opt-in): an exchange whose every
+    message stays on this rank (a whole cube on one rank) runs as ONE launch that packs and
+    rotates (ghx_cs_exchange_self); any other exchange takes the usual three launches."""
+    return CommunicationObject(context, fuse_rotated=fuse_rotated, **options)
 
 
 class Cube:

@@ -552,6 +552,26 @@ int ghx_cs_exchange_create(const ghx_exchange_item* items, const ghx_cs_item* cs
  * (those planned as ordinary segments included). Works on exchanges created without a device. */
 int ghx_cs_plan_info(const ghx_exchange* ex, int32_t* n_records, uint64_t* bytes,
                      int32_t* n_tiles, int32_t* n_rotated);
+/* The fused self exchange of a cubed-sphere exchange. When every message stays on this rank
+ * (every recv buffer is the send buffer of the same domain pair: a whole cube on one rank), all
+ * items fit one launch (fields and send buffers together at most 448 pointers: the launch has
+ * a pointer table of its own, not the GHX_MAX_SLOTS of the other launches), the two fields of every
+ * message agree in element size, components and layout order, and no send box reaches into a
+ * halo the exchange writes, ghx_cs_exchange_create also plans ONE launch (k_self_cs) that does
+ * what ghx_exchange_pack + ghx_exchange_unpack do: spaces whose pack and unpack segments cover the
+ * same bytes with the same rows run as ghx_exchange_self runs them (*n_pair_tiles workgroup
+ * tiles); the others (*n_x_records spaces: the transformed ones, and ordinary ones whose rows
+ * differ between the two sides) run element by element, sending field -> buffer and -> receiving
+ * field, rotated and negated in registers (*n_x_tiles tiles). ghx_cs_self_info works without a
+ * device; with *fusable = 0, ghx_last_error() holds the reason. ghx_cs_exchange_self has
+ * ghx_exchange_self's argument contract (the buffers are the send buffers, which hold the packed
+ * message afterwards) and fails with GHX_ERR_INVALID on an exchange that is not fusable or whose
+ * send side has parity set (ghx_exchange_set_parity, direction 0). ghx_exchange_self_fusable,
+ * ghx_exchange_mixed and the refusals above are unchanged by it. */
+int ghx_cs_self_info(const ghx_exchange* ex, int32_t* fusable, int32_t* n_pair_tiles,
+                     int32_t* n_x_records, int32_t* n_x_tiles);
+int ghx_cs_exchange_self(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                         void* const* buffers, int32_t n_buffers, ghx_stream stream);
 /* cubed_sphere::field_descriptor::unpack(const T* buffer, const IndexContainer& c, void* arg)
  * (cubed_sphere/field_descriptor.hpp:142-167) for ONE field: iteration spaces back to back from
  * `buffer`, each with its local box, global box and the global box's tile. Convenience form
