@@ -6,7 +6,9 @@ Instead of pack -> send -> recv -> unpack, every rank copies its send regions st
 receiving rank's halo cells in peer memory (xGMI on a multi-GPU node), one launch per group of
 up to 64 messages (libghx ghx_put_*: the pack plan of the source side and the unpack plan of the
 target side address the same message positions, so a lane moves element p register-to-register). Self messages are
-the same copy inside one field.
+the same copy inside one field. Cubed-sphere fields take the object in its cubed-sphere mode
+(structured.cubed_sphere.make_bulk_communication_object): its plans come from ghx_cs_put_create,
+whose launch (k_put_cs) also rotates and sign-flips the halos that cross a cube edge.
 
 Usage mirrors the reference:
     bco = make_bulk_communication_object(ctx)
@@ -119,6 +121,77 @@ def epochs_error(ep, hosts=None, me=None):
     return f"epoch error code {v}"
 
 
+CS_ELEM_SIZES = (1, 2, 4, 8, 16)
+
+
+def field_groups(bis):
+    """j-th field of each domain on this rank: per field (domain_id, j)."""
+    seen, out = {}, []
+    for bi in bis:
+        d = bi.field.domain_id()
+        j = seen.get(d, 0)
+        seen[d] = j + 1
+        out.append((d, j))
+    return out
+
+
+def field_records(bis, groups, export=True):
+    """What a rank contributes to the setup all-gather: per field its domain, its index j among
+    the domain's fields, its descriptor bytes, its IPC handle and offset (export=False leaves
+    them out: several emulated ranks of one process address each other's memory directly) and
+    its receive halos as (remote id, tag, spaces). A plain field's spaces are (local first, local
+    last); a cubed-sphere field's record also carries its CsItem bytes ("cs") and each of its
+    spaces the global box and its tile: (local first, local last, global first, global last,
+    tile) — what ghx_cs_put_create needs of the receiving side."""
+    out = []
+    for bi, (d, j) in zip(bis, groups):
+        rec = {"domain": d, "j": j, "desc": bytes(bi.field.desc)}
+        if export:
+            h = (ctypes.c_ubyte * 64)()
+            off = ctypes.c_uint64()
+            _ghx.call("ghx_ipc_export", ctypes.c_void_p(bi.field.data_ptr()), h, ctypes.byref(off))
+            rec["ipc"], rec["offset"] = bytes(h), off.value
+        halos = bi.pattern_container.recv_halos(bi.local_index)
+        cs = getattr(bi.field, "cs_item", None)
+        if cs is None:
+            rec["recv"] = [(rid, tag, [(sp[0], sp[1]) for sp in spaces])
+                           for rid, rr, tag, spaces in halos]
+        else:
+            rec["cs"] = bytes(cs)
+            tiles = bi.pattern_container.halo_tiles(bi.local_index, 1)
+            rec["recv"] = [(rid, tag, [(sp[0], sp[1], sp[2], sp[3], t)
+                                       for sp, t in zip(spaces, ts)])
+                           for (rid, rr, tag, spaces), ts in zip(halos, tiles)]
+        out.append(rec)
+    return out
+
+
+def cs_put_args(chunk, allr):
+    """ghx_cs_put_create's three per-target-entry arguments for one chunk of put_messages over
+    cubed-sphere field records: (CsItem array, array of global-box arrays, array of tile arrays,
+    keep-alive list), entry b = message b as in put_entries."""
+    n = len(chunk)
+    items = (_ghx.CsItem * max(1, n))()
+    gptr = (ctypes.POINTER(_ghx.Box) * max(1, n))()
+    tptr = (ctypes.POINTER(ctypes.c_int32) * max(1, n))()
+    keep = [items, gptr, tptr]
+    for b, (k, sps, tgt, tsps) in enumerate(chunk):
+        rec = allr[tgt[0]]["fields"][tgt[1]]
+        if "cs" not in rec:
+            raise RuntimeError("the target field of a cubed-sphere put is not a cubed-sphere field")
+        items[b] = _ghx.CsItem.from_buffer_copy(rec["cs"])
+        boxes = (_ghx.Box * max(1, len(tsps)))()
+        tiles = (ctypes.c_int32 * max(1, len(tsps)))()
+        for i, sp in enumerate(tsps):
+            for d in range(3):
+                boxes[i].first[d], boxes[i].last[d] = sp[2][d], sp[3][d]
+            tiles[i] = sp[4]
+        keep += [boxes, tiles]
+        gptr[b] = ctypes.cast(boxes, ctypes.POINTER(_ghx.Box))
+        tptr[b] = ctypes.cast(tiles, ctypes.POINTER(ctypes.c_int32))
+    return items, gptr, tptr, keep
+
+
 def put_messages(bis, groups, allr, local):
     """The node-local messages of this rank's fields, as (source field index k, send spaces,
     target (rank, field index), target spaces): each send halo of field k (domain d, its j-th
@@ -181,7 +254,8 @@ def put_entries(chunk, srcs, dsts, src_descs, allr):
         for e, desc, slot, spaces in ((src[b], src_descs[k], srcs.index(k), sps),
                                       (dst[b], tdesc, dsts.index(tgt), tsps)):
             arr = (_ghx.Box * max(1, len(spaces)))()
-            for i, (lf, ll) in enumerate(spaces):
+            for i, sp in enumerate(spaces):
+                lf, ll = sp[0], sp[1]  # cubed-sphere receive spaces carry more (field_records)
                 for d in range(len(lf)):
                     arr[i].first[d], arr[i].last[d] = lf[d], ll[d]
             keep.append(arr)
@@ -232,10 +306,13 @@ class BulkHandle:
 
 class BulkCommunicationObject:
     def __init__(self, context, epochs: str = "device", timeout: float = 30.0,
-                 remote_options=None):
+                 remote_options=None, cubed_sphere: bool = False):
         if epochs not in ("device", "host"):
             raise ValueError("epochs must be 'device' (stream-ordered flags) or 'host' (barriers)")
         self.context = context
+        # cubed-sphere mode (structured.cubed_sphere.make_bulk_communication_object): only
+        # cubed-sphere fields, put plans from ghx_cs_put_create (rotating puts, k_put_cs)
+        self.cubed_sphere = bool(cubed_sphere)
         self.epochs = epochs
         self.timeout = float(timeout)
         # options of the buffered CommunicationObject that carries halos to/from other hosts
@@ -255,10 +332,19 @@ class BulkCommunicationObject:
             raise RuntimeError("error: this bulk communication object has been initialized already")
         if bi.field.kind != 0:
             raise TypeError("bulk (zero-copy) exchange is implemented for structured fields")
-        if getattr(bi.field, "cs_item", None) is not None:
-            # a put copies field to field in the sender's orientation: it cannot rotate a halo
-            # that crosses a cube edge (ghx_put_create knows fields and boxes only)
-            raise ValueError("bulk (zero-copy) exchange does not take cubed-sphere fields")
+        is_cs = getattr(bi.field, "cs_item", None) is not None
+        if is_cs and not self.cubed_sphere:
+            # a plain put copies field to field in the sender's orientation: it cannot rotate a
+            # halo that crosses a cube edge (ghx_put_create knows fields and boxes only)
+            raise ValueError("bulk (zero-copy) exchange does not take cubed-sphere fields: use "
+                             "structured.cubed_sphere.make_bulk_communication_object")
+        if self.cubed_sphere:
+            if not is_cs:
+                raise ValueError("a cubed-sphere bulk exchange takes cubed-sphere fields only")
+            # refused here, before any collective step: a rotating put moves whole elements
+            if bi.field.desc.elem_size not in CS_ELEM_SIZES:
+                raise ValueError(f"a cubed-sphere bulk exchange takes elements of 1, 2, 4, 8 or 16 "
+                                 f"bytes, not {bi.field.desc.elem_size}")
         self._bis.append(bi)
 
     def add_fields(self, *bis):
@@ -270,13 +356,7 @@ class BulkCommunicationObject:
 
     def _field_groups(self):
         """j-th field of each domain on this rank: (domain_id, j) -> field index."""
-        seen, out = {}, []
-        for bi in self._bis:
-            d = bi.field.domain_id()
-            j = seen.get(d, 0)
-            seen[d] = j + 1
-            out.append((d, j))
-        return out
+        return field_groups(self._bis)
 
     def init(self):
         if self._initialized:
@@ -285,15 +365,7 @@ class BulkCommunicationObject:
         world = self.context.size()
         groups = self._field_groups()
         host = hostname()
-        mine = {"host": host, "fields": []}
-        for bi, (d, j) in zip(self._bis, groups):
-            h = (ctypes.c_ubyte * 64)()
-            off = ctypes.c_uint64()
-            _ghx.call("ghx_ipc_export", ctypes.c_void_p(bi.field.data_ptr()), h, ctypes.byref(off))
-            recv = [(rid, tag, [(sp[0], sp[1]) for sp in spaces])
-                    for rid, rr, tag, spaces in bi.pattern_container.recv_halos(bi.local_index)]
-            mine["fields"].append({"domain": d, "j": j, "desc": bytes(bi.field.desc),
-                                   "ipc": bytes(h), "offset": off.value, "recv": recv})
+        mine = {"host": host, "fields": field_records(self._bis, groups)}
         allr = self.context.all_gather_object(mine)
         local = sorted(r for r, info in enumerate(allr) if info["host"] == host)
         remote = [r for r in range(world) if r not in local]
@@ -343,7 +415,12 @@ class BulkCommunicationObject:
         src, dst, keep = put_entries(chunk, srcs, dsts, [bi.field.desc for bi in self._bis], allr)
         n = len(chunk)
         h = ctypes.c_void_p()
-        _ghx.call("ghx_put_create", src, n, dst, n, ctypes.byref(h))
+        if self.cubed_sphere:
+            items, gptr, tptr, more = cs_put_args(chunk, allr)
+            _ghx.call("ghx_cs_put_create", src, n, dst, n, items, gptr, tptr, ctypes.byref(h))
+            keep = keep + more
+        else:
+            _ghx.call("ghx_put_create", src, n, dst, n, ctypes.byref(h))
         sp = _ghx.ptr_array([self._bis[k].field.data_ptr() for k in srcs])
         dp = _ghx.ptr_array([ptr_of[t] for t in dsts])
         self._keep.append(keep)

@@ -301,35 +301,6 @@ const char* get_error() { return g_error.c_str(); }
 
 }  // namespace ghx
 
-// Put plan: the pack plan of the source side and the unpack plan of the target side, segment k
-// of each covering the same virtual message bytes (checked). The launch is tiled by the source
-// plan's tile table alone (k_put addresses the target segment by message position), so the
-// target plan's own tiling is not compared: the two sides size their short-row tiles by their
-// own fields' rows (one source field, one target field per peer) and differ at large sizes.
-struct ghx_put
-{
-    std::unique_ptr<ghx::splan> from, to;
-    ghx_put(const ghx_pack_entry* src, int n_src, const ghx_pack_entry* dst, int n_dst)
-    : from(new ghx::splan(src, n_src, 0)), to(new ghx::splan(dst, n_dst, 1))
-    {
-        bool ok = from->host_segs.size() == to->host_segs.size() && from->bytes == to->bytes;
-        for (size_t k = 0; ok && k < from->host_segs.size(); ++k)
-        {
-            const auto& a = from->host_segs[k];
-            const auto& b = to->host_segs[k];
-            ok = ghx::exchange_plan::same_message(a, b) && a.n_outer == b.n_outer;
-            for (int d = 0; ok && d < 4; ++d) ok = a.ext[d] == b.ext[d];
-        }
-        if (!ok)
-            throw ghx::invalid("source and target iteration spaces do not describe the same "
-                               "message bytes (shapes, order, element sizes or row structure differ)");
-        if (from->grouped() || to->grouped())
-            throw ghx::invalid("a put plan takes at most 64 source and 64 target fields (one launch)");
-        ghx::upload_pair_records(recs, from->host_segs, to->host_segs, from->host_tiles);
-    }
-    ghx::device_tables recs;  // pair records (source segment with tile index, target segment)
-};
-
 using namespace ghx;
 
 namespace
@@ -685,6 +656,157 @@ int check_ptr(const void* p, const char* what)
 {
     if (!p) throw invalid(std::string("null argument: ") + what);
     return 0;
+}
+
+// The put plan of ghx_cs_put_create (cs_put_plan, k_put_cs): build_cs_self's pairing without the
+// buffer. Each target space (dst[k]'s box b with its global box and tile) is matched with the
+// source space at the same virtual message bytes; spaces cs_plan_space plans as ordinary segments
+// that the sender's add_box_segments match one to one become pair records, every other space put
+// tile records. Throws `invalid` with the reason for what a put cannot serve.
+std::unique_ptr<cs_put_plan> build_cs_put(const ghx_pack_entry* src, int n_src,
+                                          const ghx_pack_entry* dst, int n_dst,
+                                          const ghx_cs_item* cs, const ghx_box* const* global,
+                                          const int32_t* const* tiles)
+{
+    auto space_bytes = [](const ghx_pack_entry& e, const ghx_box& b) {
+        uint64_t n = uint64_t(e.field.num_components) * uint64_t(e.field.elem_size);
+        for (int d = 0; d < 3; ++d)
+        {
+            if (b.last[d] < b.first[d]) throw invalid("iteration space: first must be <= last");
+            n *= uint64_t(int64_t(b.last[d]) - b.first[d] + 1);
+        }
+        return n;
+    };
+    auto check_entry = [](const ghx_pack_entry& e) {
+        validate_field(e.field);
+        if (e.field.dim - (e.field.has_components ? 1 : 0) != 3)
+            throw invalid("a cubed-sphere field has the three spatial dimensions x, y, z");
+        if (e.field_slot < 0 || e.buffer_slot < 0) throw invalid("negative slot");
+        if (e.field_slot >= GHX_MAX_SLOTS)
+            throw invalid("a put plan takes at most 64 source and 64 target fields (one launch)");
+        if (e.n_boxes < 0 || (e.n_boxes > 0 && !e.boxes)) throw invalid("bad boxes");
+    };
+    // the source spaces by the message bytes they occupy
+    struct sspace
+    {
+        const ghx_pack_entry* e;
+        const ghx_box* box;
+    };
+    std::map<std::pair<int32_t, uint64_t>, sspace> by_bytes;
+    size_t n_src_spaces = 0;
+    for (int k = 0; k < n_src; ++k)
+    {
+        const ghx_pack_entry& e = src[k];
+        check_entry(e);
+        uint64_t off = e.buffer_offset;
+        for (int b = 0; b < e.n_boxes; ++b)
+        {
+            const ghx_box& s = e.boxes[b];
+            // below local cell 0 lies the sender's own halo, which its sources may be writing
+            if (s.first[0] < 0 || s.first[1] < 0 || s.first[2] < 0)
+                throw invalid("a source box reaches into its field's halo (it starts below local cell 0)");
+            if (!by_bytes.emplace(std::make_pair(e.buffer_slot, off), sspace{&e, &s}).second)
+                throw invalid("two source spaces at the same message bytes");
+            off += space_bytes(e, s);
+            ++n_src_spaces;
+        }
+    }
+    std::vector<seg_s> from, to;
+    std::vector<int32_t> gs, gd;
+    std::vector<xsbox> boxes;
+    uint64_t bytes = 0;
+    size_t n_dst_spaces = 0;
+    for (int k = 0; k < n_dst; ++k)
+    {
+        const ghx_pack_entry& re = dst[k];
+        check_entry(re);
+        check_cs_item(re.field, cs[k]);
+        if (re.n_boxes > 0 && (!global[k] || !tiles[k]))
+            throw invalid("a target entry without the global boxes or tiles of its spaces");
+        const ghx_field_desc& fr = re.field;
+        uint64_t off = re.buffer_offset;
+        for (int b = 0; b < re.n_boxes; ++b, ++n_dst_spaces)
+        {
+            const auto it = by_bytes.find({re.buffer_slot, off});
+            if (it == by_bytes.end())
+                throw invalid("a target space has no source space at the same message bytes");
+            const ghx_pack_entry& se = *it->second.e;
+            const ghx_box& sbox = *it->second.box;
+            const ghx_field_desc& fs = se.field;
+            bool same = fs.elem_size == fr.elem_size && fs.dim == fr.dim &&
+                        fs.has_components == fr.has_components && fs.num_components == fr.num_components;
+            for (int d = 0; same && d < fr.dim; ++d) same = fs.layout[d] == fr.layout[d];
+            if (!same)
+                throw invalid("the two fields of a message differ in element size, components or "
+                              "layout order (the message's axis order differs between the two sides)");
+            is_pair sp{};
+            for (int d = 0; d < 3; ++d)
+            {
+                sp.lf[d] = re.boxes[b].first[d];
+                sp.ll[d] = re.boxes[b].last[d];
+                sp.gf[d] = global[k][b].first[d];
+                sp.gl[d] = global[k][b].last[d];
+            }
+            // the message is the dense box in the sender's coordinates, which are the global
+            // box's: the source box must have its shape (the target's under the transform)
+            for (int d = 0; d < 3; ++d)
+                if (int64_t(sbox.last[d]) - sbox.first[d] != int64_t(sp.gl[d]) - sp.gf[d])
+                    throw invalid("a source box and its target box differ in shape under the tile transform");
+            cs_recv_plan rp;
+            uint64_t nb = 0;
+            cs_plan_space(rp, fr, cs[k], sp, tiles[k][b], re.field_slot, re.buffer_slot, off, &nb);
+            std::vector<seg_s> ps;
+            add_box_segments(ps, fs, sbox, 0, 0, off);  // also checks the source's bounds
+            bool paired = rp.xs.empty() && ps.size() == rp.segs.size();
+            for (size_t i = 0; paired && i < ps.size(); ++i)
+                paired = exchange_plan::same_message(ps[i], rp.segs[i]);
+            if (paired)
+            {
+                for (size_t i = 0; i < ps.size(); ++i)
+                {
+                    from.push_back(ps[i]);
+                    to.push_back(rp.segs[i]);
+                    gs.push_back(se.field_slot);
+                    gd.push_back(re.field_slot);
+                }
+            }
+            else
+            {
+                const int64_t elem = fr.elem_size;
+                if (elem > 16 || (elem & (elem - 1)))
+                    throw invalid("a space that cannot be paired holds elements that are not 1, 2, 4, 8 or 16 bytes");
+                xsbox x{};
+                x.dst = rp.xs.empty() ? cs_space_box(fr, cs[k], sp, tiles[k][b], re.field_slot, 0, off)
+                                      : rp.xs[0];
+                // the sending side of the same dense box: its axes are the sender's dims in
+                // layout order, fastest first — the receiver's order, the layouts being equal
+                const int D = fs.dim;
+                int by_speed[GHX_MAX_DIM];
+                for (int d = 0; d < D; ++d) by_speed[D - 1 - fs.layout[d]] = d;
+                x.src_off = 0;
+                for (int d = 0; d < 3; ++d)
+                    x.src_off += (int64_t(sbox.first[d]) + fs.offsets[d]) * fs.byte_strides[d];
+                for (int a = 0; a < 4; ++a) x.src_stride[a] = 0;
+                for (int a = 0; a < D; ++a)
+                {
+                    const int d = by_speed[a];
+                    const int64_t ext = d < 3 ? int64_t(sbox.last[d]) - sbox.first[d] + 1
+                                              : int64_t(fs.num_components);
+                    if (ext != int64_t(x.dst.ext[a]))
+                        throw invalid("a source box and its target box differ in shape under the tile transform");
+                    x.src_stride[a] = fs.byte_strides[d];
+                }
+                x.src_slot = se.field_slot;
+                boxes.push_back(x);
+            }
+            bytes += nb;
+            off += nb;
+        }
+    }
+    if (n_dst_spaces != n_src_spaces)
+        throw invalid("source and target iteration spaces do not describe the same message bytes "
+                      "(a source space has no target space)");
+    return std::make_unique<cs_put_plan>(from, to, gs, gd, boxes, bytes);
 }
 }  // namespace
 
@@ -1781,11 +1903,46 @@ int ghx_put_create(const ghx_pack_entry* src, int32_t n_src, const ghx_pack_entr
     });
 }
 
+int ghx_cs_put_create(const ghx_pack_entry* src, int32_t n_src, const ghx_pack_entry* dst,
+                      int32_t n_dst, const ghx_cs_item* dst_cs, const ghx_box* const* dst_global,
+                      const int32_t* const* dst_tiles, ghx_put** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        *out = nullptr;
+        if (n_src < 0 || n_dst < 0 || (n_src && !src) || (n_dst && !dst))
+            throw invalid("bad entry arrays");
+        if (n_dst && (!dst_cs || !dst_global || !dst_tiles))
+            throw invalid("null argument: the target entries' cubed-sphere items, global boxes or tiles");
+        *out = new ghx_put(build_cs_put(src, n_src, dst, n_dst, dst_cs, dst_global, dst_tiles));
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_put_info(const ghx_put* put, int32_t* n_pair_tiles, int32_t* n_x_records,
+                    int32_t* n_x_tiles)
+{
+    return guarded([&] {
+        check_ptr(put, "put");
+        const cs_put_plan* p = put->cs.get();
+        if (n_pair_tiles) *n_pair_tiles = p ? int32_t(p->n_pair_tiles()) : int32_t(put->from->n_tiles);
+        if (n_x_records) *n_x_records = p ? p->n_x_records : 0;
+        if (n_x_tiles) *n_x_tiles = p ? int32_t(p->n_x_tiles()) : 0;
+        return GHX_OK;
+    });
+}
+
 int ghx_put_execute(const ghx_put* put, void* const* src_fields, int32_t n_src,
                     void* const* dst_fields, int32_t n_dst, ghx_stream stream)
 {
     return guarded([&] {
         check_ptr(put, "put");
+        if (put->cs)
+        {
+            check_ptr(src_fields, "src_fields");
+            check_ptr(dst_fields, "dst_fields");
+            return put->cs->execute(src_fields, n_src, dst_fields, n_dst, stream);
+        }
         const splan& p = *put->from;
         const splan& q = *put->to;
         if (p.n_tiles == 0) return int(GHX_OK);
@@ -1816,6 +1973,12 @@ int ghx_put_info(const ghx_put* put, uint64_t* bytes, int32_t* n_tiles)
 {
     return guarded([&] {
         check_ptr(put, "put");
+        if (put->cs)
+        {
+            if (bytes) *bytes = put->cs->bytes;
+            if (n_tiles) *n_tiles = int32_t(put->cs->n_pair_tiles() + put->cs->n_x_tiles());
+            return GHX_OK;
+        }
         if (bytes) *bytes = put->from->bytes;
         if (n_tiles) *n_tiles = int32_t(put->from->n_tiles);
         return GHX_OK;

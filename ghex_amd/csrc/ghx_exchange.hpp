@@ -157,3 +157,35 @@ struct exchange_plan
 struct ghx_exchange : ghx::exchange_plan
 {
 };
+
+// Put plan: the pack plan of the source side and the unpack plan of the target side, segment k
+// of each covering the same virtual message bytes (checked). The launch is tiled by the source
+// plan's tile table alone (k_put addresses the target segment by message position), so the
+// target plan's own tiling is not compared: the two sides size their short-row tiles by their
+// own fields' rows (one source field, one target field per peer) and differ at large sizes.
+struct ghx_put
+{
+    std::unique_ptr<ghx::splan> from, to;
+    ghx_put(const ghx_pack_entry* src, int n_src, const ghx_pack_entry* dst, int n_dst)
+    : from(new ghx::splan(src, n_src, 0)), to(new ghx::splan(dst, n_dst, 1))
+    {
+        bool ok = from->host_segs.size() == to->host_segs.size() && from->bytes == to->bytes;
+        for (size_t k = 0; ok && k < from->host_segs.size(); ++k)
+        {
+            const auto& a = from->host_segs[k];
+            const auto& b = to->host_segs[k];
+            ok = ghx::exchange_plan::same_message(a, b) && a.n_outer == b.n_outer;
+            for (int d = 0; ok && d < 4; ++d) ok = a.ext[d] == b.ext[d];
+        }
+        if (!ok)
+            throw ghx::invalid("source and target iteration spaces do not describe the same "
+                               "message bytes (shapes, order, element sizes or row structure differ)");
+        if (from->grouped() || to->grouped())
+            throw ghx::invalid("a put plan takes at most 64 source and 64 target fields (one launch)");
+        ghx::upload_pair_records(recs, from->host_segs, to->host_segs, from->host_tiles);
+    }
+    ghx::device_tables recs;  // pair records (source segment with tile index, target segment)
+    // a put made by ghx_cs_put_create: `cs` alone (pair records and put tile records, k_put_cs)
+    std::unique_ptr<ghx::cs_put_plan> cs;
+    explicit ghx_put(std::unique_ptr<ghx::cs_put_plan> p) : cs(std::move(p)) {}
+};

@@ -250,6 +250,20 @@ struct kargs_cs
 };
 static_assert(sizeof(kargs_cs) < 4096, "kargs_cs is passed by value");
 
+// Arguments of the cubed-sphere put (k_put_cs): blocks [0, n_pair_tiles) take the pair record
+// (two seg_s, as k_put's record form) at their index, the next n_x_tiles a put tile record
+// (seg_xs, buffer side unused). Source field slot s at src_ptr[s], target field slot d at
+// dst_ptr[d], as k_put's field_ptr / buf_ptr.
+struct kargs_pcs
+{
+    const void* pair_recs;
+    const void* x_recs;
+    uint32_t n_pair_tiles;
+    uint32_t n_x_tiles;
+    uint64_t src_ptr[GHX_MAX_SLOTS];
+    uint64_t dst_ptr[GHX_MAX_SLOTS];
+};
+
 // Double-buffered buffers (the direct exchange's one-launch epochs, ghx_epochs.hip): a buffer
 // exists twice, its odd-parity copy `offset` bytes after the even one, and a launch uses the copy
 // of the exchange's parity, read on the device from the epoch counter (so that a captured graph
@@ -285,6 +299,7 @@ int launch_self(const kargs& a, void* stream, uint32_t grid);
 int launch_put(const kargs& a, void* stream, uint32_t grid);
 int launch_unpack_x(const kargs& a, void* stream, uint32_t grid);  // tile_recs: seg_x records
 int launch_self_cs(const kargs_cs& a, void* stream, uint32_t grid);
+int launch_put_cs(const kargs_pcs& a, void* stream, uint32_t grid);
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

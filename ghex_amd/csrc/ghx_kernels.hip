@@ -1169,6 +1169,135 @@ __global__ __launch_bounds__(kBlock) void k_self_cs(kargs_cs a)
     }
 }
 
+// Cubed-sphere put: k_self_cs's walk without the buffer, the destination being
+// any mapped field (this device's or a node-local peer's through IPC). Blocks [0, n_pair_tiles)
+// take a pair record and do what k_put's record form does with it; the blocks after them take a
+// put tile record (seg_xs, buffer side unused): each lane loads ONE element from the sending
+// field, negates it in registers as unpack_x_tile negates, and stores it to the receiving field
+// — 2 bytes of traffic per message byte against k_self_cs's 3. The record's axes are sorted by
+// ascending |stride| of the RECEIVING field, so a wave's stores cover whole destination runs (the
+// side that may cross xGMI), and its loads fall on a few row pieces of the sending field. Plain
+// global stores only: the epochs' system-scope release at close covers nothing else. No LDS, no
+// barrier; the planner refuses source boxes that reach into the sender's halo.
+template<int E>
+__device__ __forceinline__ void put_x_tile(const seg_xs& r, const char* __restrict__ src,
+                                           char* __restrict__ field, bool aligned)
+{
+    using V = typename vec_t<(1 << E)>::type;
+    const seg_x& s = r.x;
+    const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
+    for (uint32_t i = threadIdx.x; i < total; i += kBlock)
+    {
+        const uint32_t q0 = fastdiv(i, s.mag[0]);
+        const uint32_t c0 = i - q0 * s.tdim[0];
+        const uint32_t q1 = fastdiv(q0, s.mag[1]);
+        const uint32_t c1 = q0 - q1 * s.tdim[1];
+        const uint32_t c3 = fastdiv(q1, s.mag[2]);
+        const uint32_t c2 = q1 - c3 * s.tdim[2];
+        if (c0 >= s.act[0] || c1 >= s.act[1] || c2 >= s.act[2] || c3 >= s.act[3]) continue;
+        const char* from = src + r.src_off + int64_t(c0) * r.src_stride[0] +
+                           int64_t(c1) * r.src_stride[1] + int64_t(c2) * r.src_stride[2] +
+                           int64_t(c3) * r.src_stride[3];
+        V v;
+        if (aligned) v = vload<V>(from);
+        else
+        {
+            // a field whose base or strides are not multiples of the element size
+            unsigned char b[1 << E];
+#pragma unroll
+            for (int k = 0; k < (1 << E); ++k) b[k] = vload<unsigned char>(from + k);
+            __builtin_memcpy(&v, b, sizeof(V));
+        }
+        if (s.neg_mask)
+        {
+            uint32_t comp = s.comp0;
+            if (s.comp_pos < 4) comp += s.comp_pos == 0 ? c0 : s.comp_pos == 1 ? c1 : s.comp_pos == 2 ? c2 : c3;
+            if (comp < 2 && ((s.neg_mask >> comp) & 1u))
+            {
+                if constexpr (E == 2)
+                    v = s.neg_kind == 1 ? (v ^ 0x80000000u) : (0u - v);
+                else if constexpr (E == 3)
+                {
+                    if (s.neg_kind == 1) v.y ^= 0x80000000u;
+                    else
+                    {
+                        const uint64_t w = 0ull - ((uint64_t(v.y) << 32) | v.x);
+                        v.x = uint32_t(w);
+                        v.y = uint32_t(w >> 32);
+                    }
+                }
+            }
+        }
+        char* dst = field + s.field_off + int64_t(c0) * s.stride[0] + int64_t(c1) * s.stride[1] +
+                    int64_t(c2) * s.stride[2] + int64_t(c3) * s.stride[3];
+        if (aligned) vstore<V>(dst, v);
+        else
+        {
+            unsigned char b[1 << E];
+            __builtin_memcpy(b, &v, sizeof(V));
+#pragma unroll
+            for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(dst + k, b[k]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_put_cs(kargs_pcs a)
+{
+    const seg_s* __restrict__ pairs = static_cast<const seg_s*>(a.pair_recs);
+    const seg_xs* __restrict__ xrecs = static_cast<const seg_xs*>(a.x_recs);
+    const uint32_t n_tiles = a.n_pair_tiles + a.n_x_tiles;
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x)
+    {
+        if (t < a.n_pair_tiles)  // uniform per workgroup
+        {
+            const seg_s s = pairs[2 * t];
+            const seg_s q = pairs[2 * t + 1];
+            const uint32_t start = s.first_tile * s.tile_bytes;
+            const uint32_t end = min(start + s.tile_bytes, s.bytes);
+            const char* src = reinterpret_cast<const char*>(a.src_ptr[s.field_slot]);
+            char* dst = reinterpret_cast<char*>(a.dst_ptr[q.field_slot]);
+            int w = min(int(s.wlog2), int(q.wlog2));
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(src)));
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(dst)));
+            if (s.amode == 1 && q.amode == 1 && w >= 3)
+            {
+                if (w == 4) copy_direct<16, 1>(s, q, src, dst, start, end);
+                else copy_direct<8, 1>(s, q, src, dst, start, end);
+                continue;
+            }
+            switch (w)
+            {
+                case 4: copy_direct<16>(s, q, src, dst, start, end); break;
+                case 3: copy_direct<8>(s, q, src, dst, start, end); break;
+                case 2: copy_direct<4>(s, q, src, dst, start, end); break;
+                case 1: copy_direct<2>(s, q, src, dst, start, end); break;
+                default: copy_direct<1>(s, q, src, dst, start, end); break;
+            }
+            continue;
+        }
+        const seg_xs r = xrecs[t - a.n_pair_tiles];
+        const char* src = reinterpret_cast<const char*>(a.src_ptr[r.src_slot]);
+        char* field = reinterpret_cast<char*>(a.dst_ptr[r.x.field_slot]);
+        // element-wide accesses when the source, the destination and every stride are
+        // element-aligned (uniform per tile; a mapped peer pointer's alignment is a run-time fact)
+        const uint64_t em = (1u << r.x.elog2) - 1u;
+        const bool aligned =
+            ((reinterpret_cast<uint64_t>(src) + uint64_t(r.src_off)) & em) == 0 &&
+            ((reinterpret_cast<uint64_t>(field) + uint64_t(r.x.field_off)) & em) == 0 &&
+            ((uint64_t(r.x.stride[0]) | uint64_t(r.x.stride[1]) | uint64_t(r.x.stride[2]) |
+              uint64_t(r.x.stride[3]) | uint64_t(r.src_stride[0]) | uint64_t(r.src_stride[1]) |
+              uint64_t(r.src_stride[2]) | uint64_t(r.src_stride[3])) & em) == 0;
+        switch (r.x.elog2)
+        {
+            case 4: put_x_tile<4>(r, src, field, aligned); break;
+            case 3: put_x_tile<3>(r, src, field, aligned); break;
+            case 2: put_x_tile<2>(r, src, field, aligned); break;
+            case 1: put_x_tile<1>(r, src, field, aligned); break;
+            default: put_x_tile<0>(r, src, field, aligned); break;
+        }
+    }
+}
+
 int launched(const char* what)
 {
     const hipError_t e = hipGetLastError();
@@ -1288,6 +1417,14 @@ int launch_self_cs(const kargs_cs& a, void* stream, uint32_t grid)
     if (n_tiles == 0) return GHX_OK;
     launch(k_self_cs, min(grid, n_tiles), static_cast<hipStream_t>(stream), a);
     return launched("cubed-sphere self-exchange");
+}
+
+int launch_put_cs(const kargs_pcs& a, void* stream, uint32_t grid)
+{
+    const uint32_t n_tiles = a.n_pair_tiles + a.n_x_tiles;
+    if (n_tiles == 0) return GHX_OK;
+    launch(k_put_cs, min(grid, n_tiles), static_cast<hipStream_t>(stream), a);
+    return launched("cubed-sphere put");
 }
 
 template<bool DBL, bool REC>

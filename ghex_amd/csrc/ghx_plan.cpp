@@ -878,6 +878,123 @@ int cs_self_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// cubed-sphere put
+// ---------------------------------------------------------------------------------------------
+cs_put_plan::cs_put_plan(const std::vector<seg_s>& from, const std::vector<seg_s>& to,
+                         const std::vector<int32_t>& gs, const std::vector<int32_t>& gd,
+                         const std::vector<xsbox>& boxes, uint64_t nbytes)
+: bytes(nbytes)
+{
+    if (from.size() != to.size() || gs.size() != from.size() || gd.size() != from.size())
+        throw invalid("put plan: one target segment and one slot pair per source segment");
+    auto slot = [&](int32_t s, int32_t d) {
+        if (s < 0 || d < 0) throw invalid("negative slot");
+        if (s >= GHX_MAX_SLOTS || d >= GHX_MAX_SLOTS)
+            throw invalid("a put plan takes at most 64 source and 64 target fields (one launch)");
+        max_src_slot = std::max(max_src_slot, s);
+        max_dst_slot = std::max(max_dst_slot, d);
+    };
+    if (!from.empty())
+    {
+        std::vector<seg_s> p = from, q = to;
+        for (size_t k = 0; k < from.size(); ++k)
+        {
+            slot(gs[k], gd[k]);
+            p[k].field_slot = uint16_t(gs[k]);
+            q[k].field_slot = uint16_t(gd[k]);
+        }
+        // tiled by the source side's table alone, with the pack plans' tile sizes and dispatch
+        // order, as ghx_put_create's plans are
+        const std::vector<uint32_t> tiles = build_tiles(p, 0);
+        (void)build_tiles(q, 1);
+        pair_recs.resize(tiles.size());  // 2 per tile
+        for (size_t t = 0; t < tiles.size() / 2; ++t)
+        {
+            const uint32_t si = tiles[2 * t];
+            pair_recs[2 * t] = p[si];
+            pair_recs[2 * t].first_tile = tiles[2 * t + 1];
+            pair_recs[2 * t + 1] = q[si];
+        }
+    }
+    for (const xsbox& b : boxes)
+    {
+        slot(b.src_slot, b.dst.field_slot);
+        std::vector<seg_x> recs;
+        std::vector<xtile_pos> where;
+        make_tile_records(recs, b.dst, uint16_t(b.dst.field_slot), 0, &where);
+        for (size_t t = 0; t < recs.size(); ++t)
+        {
+            seg_xs r{};
+            r.x = recs[t];
+            r.src_off = b.src_off;
+            for (int k = 0; k < 4; ++k) r.src_off += int64_t(where[t].origin[k]) * b.src_stride[k];
+            for (int j = 0; j < 4; ++j) r.src_stride[j] = b.src_stride[where[t].axis[j]];
+            r.src_slot = uint16_t(b.src_slot);
+            x_recs.push_back(r);
+        }
+        ++n_x_records;
+    }
+    if (!have_device()) return;
+    if (!pair_recs.empty())
+    {
+        const size_t nb = pair_recs.size() * sizeof(seg_s);
+        if (hipMalloc(&dev.segs, nb) != hipSuccess) throw hip_error("hipMalloc(put pair records)");
+        if (hipMemcpy(dev.segs, pair_recs.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
+            throw hip_error("hipMemcpy(put pair records)");
+    }
+    if (!x_recs.empty())
+    {
+        const size_t nb = x_recs.size() * sizeof(seg_xs);
+        if (hipMalloc(&dev.recs, nb) != hipSuccess) throw hip_error("hipMalloc(put tile records)");
+        if (hipMemcpy(dev.recs, x_recs.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
+            throw hip_error("hipMemcpy(put tile records)");
+    }
+}
+
+int cs_put_plan::execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const
+{
+    const uint32_t nt = n_pair_tiles() + n_x_tiles();
+    if (nt == 0) return GHX_OK;
+    if (ns <= max_src_slot || nd <= max_dst_slot) throw invalid("pointer arrays do not cover the plan's slots");
+    if ((!pair_recs.empty() && !dev.segs) || (!x_recs.empty() && !dev.recs))
+        throw hip_error("plan has no device tables (no HIP device at creation)");
+    if (x_recs.empty())
+    {
+        // nothing to transform: k_put's record form over the pair records
+        kargs k{};
+        k.tile_recs = dev.segs;
+        k.n_tiles = n_pair_tiles();
+        for (int i = 0; i <= max_src_slot; ++i)
+        {
+            if (!src[i]) throw invalid("null source field pointer");
+            k.field_ptr[i] = reinterpret_cast<uint64_t>(src[i]);
+        }
+        for (int i = 0; i <= max_dst_slot; ++i)
+        {
+            if (!dst[i]) throw invalid("null target field pointer");
+            k.buf_ptr[i] = reinterpret_cast<uint64_t>(dst[i]);
+        }
+        return launch_put(k, stream, grid_for_tiles(k.n_tiles));
+    }
+    kargs_pcs a{};
+    a.pair_recs = dev.segs;
+    a.x_recs = dev.recs;
+    a.n_pair_tiles = n_pair_tiles();
+    a.n_x_tiles = n_x_tiles();
+    for (int i = 0; i <= max_src_slot; ++i)
+    {
+        if (!src[i]) throw invalid("null source field pointer");
+        a.src_ptr[i] = reinterpret_cast<uint64_t>(src[i]);
+    }
+    for (int i = 0; i <= max_dst_slot; ++i)
+    {
+        if (!dst[i]) throw invalid("null target field pointer");
+        a.dst_ptr[i] = reinterpret_cast<uint64_t>(dst[i]);
+    }
+    return launch_put_cs(a, stream, grid_for_tiles(nt));
+}
+
+// ---------------------------------------------------------------------------------------------
 // unstructured
 // ---------------------------------------------------------------------------------------------
 uplan::uplan(const ghx_upack_entry* entries, int n_entries, int dir) : direction(dir)

@@ -152,6 +152,34 @@ struct cs_self_plan
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
 
+// Cubed-sphere put (k_put_cs): the zero-copy form of the walk above. Spaces whose
+// source and target segments cover the same message bytes with the same rows become pair records
+// and run as k_put runs them; every other space becomes put tile records: seg_xs whose buffer
+// side (x.buf_off, x.buf_slot, x.bstride) is unused — each lane loads one element from the
+// sending field and stores it, negated as `x` says, to the receiving field, which may be a peer's
+// IPC-mapped memory. Field slots: the sender's (pair primary, seg_xs::src_slot) index the
+// source pointer array, the receiver's (pair companion, x.field_slot) the target pointer array;
+// fewer than GHX_MAX_SLOTS of each (one launch). Built without a device like cs_self_plan.
+struct cs_put_plan
+{
+    std::vector<seg_s> pair_recs;  // two per pair tile: source segment (first_tile = the tile's
+                                   // index in it), then target segment
+    std::vector<seg_xs> x_recs;    // one per put tile
+    int32_t n_x_records = 0;       // spaces (boxes) behind x_recs
+    uint64_t bytes = 0;            // message bytes moved per execution
+    int max_src_slot = -1, max_dst_slot = -1;
+    device_tables dev;             // dev.segs: pair_recs, dev.recs: x_recs
+    uint32_t n_pair_tiles() const { return uint32_t(pair_recs.size() / 2); }
+    uint32_t n_x_tiles() const { return uint32_t(x_recs.size()); }
+    // source / target segments of the paired spaces (segment k of each over the same message
+    // bytes; gs / gd: the source / target field slot of each) and the boxes of the others
+    // (dst.field_slot: the target slot, src_slot: the source slot)
+    cs_put_plan(const std::vector<seg_s>& from, const std::vector<seg_s>& to,
+                const std::vector<int32_t>& gs, const std::vector<int32_t>& gd,
+                const std::vector<xsbox>& boxes, uint64_t bytes);
+    int execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const;
+};
+
 // unstructured fused plan
 struct uplan
 {

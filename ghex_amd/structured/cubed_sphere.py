@@ -6,8 +6,9 @@ Six tiles of edge_size x edge_size cells over `levels` levels, oriented as drawn
 cubed_sphere/transform.hpp:21-38. Domains are rectangles of one tile; a halo that crosses a cube
 edge is packed by the neighbour in its own coordinates and rotated (vector components also
 sign-flipped) by the receiver's unpack, which libghx runs as a second launch after the ordinary
-unpack (k_unpack_x). Fields are used with the ordinary CommunicationObject; the bulk, direct and
-pipelined exchanges refuse them."""
+unpack (k_unpack_x). Fields are used with the ordinary CommunicationObject, or with this module's
+make_bulk_communication_object (zero-copy rotating puts between node-local ranks); the plain
+bulk object and the direct and pipelined exchanges refuse them."""
 from __future__ import annotations
 
 import ctypes
@@ -25,6 +26,19 @@ def make_communication_object(context, fuse_rotated: bool = False,
     message stays on this rank (a whole cube on one rank) runs as ONE launch that packs and
     rotates (ghx_cs_exchange_self); any other exchange takes the usual three launches."""
     return CommunicationObject(context, fuse_rotated=fuse_rotated, **options)
+
+
+def make_bulk_communication_object(context, epochs: str = "device", timeout: float = 30.0,
+                                   remote_options=None):
+    """The zero-copy (bulk) exchange for cubed-sphere fields: every rank puts its send regions
+    straight into the node-local receivers' halos, rotated and sign-flipped on the way
+    (ghx_cs_put_create, one k_put_cs launch per group of <= 64 messages) — no send or receive
+    buffers. Takes cubed-sphere fields of 1-, 2-, 4-, 8- or 16-byte elements only; epochs,
+    timeout and remote_options as bulk_communication_object.make_bulk_communication_object (the
+    halos of ranks on other hosts travel through a buffered cubed-sphere exchange)."""
+    from ..bulk_communication_object import BulkCommunicationObject
+    return BulkCommunicationObject(context, epochs=epochs, timeout=timeout,
+                                   remote_options=remote_options, cubed_sphere=True)
 
 
 class Cube:

@@ -534,8 +534,9 @@ int ghx_exchange_set_parity(ghx_exchange* ex, int32_t direction, const uint64_t*
  * With one transformed (rotated) space ghx_exchange_self_fusable and ghx_exchange_mixed report
  * 0, and ghx_exchange_split and ghx_exchange_set_parity(direction 1) fail with GHX_ERR_INVALID:
  * the per-buffer, pipelined and double-buffered unpacks do not rotate. ghx_put_create sees
- * fields and boxes only and has no cubed-sphere form: do not build puts from such a pattern
- * (the Python bulk object refuses). */
+ * fields and boxes only and refuses a rotated pair of boxes: puts from a cubed-sphere pattern
+ * are built with ghx_cs_put_create (below, with the other put entry points), which takes the
+ * receiver's cubed-sphere item, global boxes and tiles as well. */
 typedef struct ghx_cs_item
 {
     int32_t tile;
@@ -611,6 +612,36 @@ int ghx_put_execute(const ghx_put* put, void* const* src_fields, int32_t n_src,
                     void* const* dst_fields, int32_t n_dst, ghx_stream stream);
 int ghx_put_info(const ghx_put* put, uint64_t* bytes, int32_t* n_tiles);
 int ghx_put_destroy(ghx_put* put);
+
+/* A put plan over cubed-sphere fields (no reference counterpart: the reference's RMA put does not
+ * rotate). src and dst are ghx_put_create's two entry arrays — the source side is the ordinary
+ * pack side of a cubed-sphere exchange, a box of the sender's field in its own coordinates, and
+ * needs no cubed-sphere item. Per target entry k: dst_cs[k], the receiving field's item as for
+ * ghx_cs_exchange_create; dst_global[k][b] and dst_tiles[k][b], the global box of the entry's
+ * b-th space and that box's tile (ghx_pattern_key_boxes / ghx_pattern_key_tiles of the
+ * receiver's recv halo). Each target space is paired with the source space at the same virtual
+ * message bytes (buffer_slot, running offset). Spaces the receiver would unpack as ordinary
+ * segments whose rows the sender's segments match one to one run as ghx_put_create's do
+ * (*n_pair_tiles workgroup tiles); every other space (*n_x_records of them: the transformed
+ * ones, and ordinary ones whose rows differ between the two sides) runs element by element —
+ * sending field -> receiving field, rotated and negated in registers (*n_x_tiles tiles; the
+ * "x_tile_elems" knob sizes them) — in the same single launch (k_put_cs). Element-wide accesses
+ * where both pointers and all strides are element-aligned at run time, byte-wide otherwise.
+ * The result is an ordinary ghx_put for ghx_put_execute / ghx_put_info (bytes = the message
+ * bytes, tiles of both kinds) / ghx_put_destroy, with the same limit of fewer than 64 source
+ * and 64 target field slots, and can be created without a device.
+ * GHX_ERR_INVALID, with the reason in ghx_last_error(), when: the two fields of a message differ
+ * in element size, components or layout order; a space that cannot be paired holds elements that
+ * are not 1, 2, 4, 8 or 16 bytes; a source box and its target box differ in shape under the tile
+ * transform; a vector field's value kind is one ghx_cs_exchange_create refuses; a source box
+ * starts below local cell 0 on any axis (it would read the sender's halo, which the sender's own
+ * sources write in the same epoch). ghx_cs_put_info on a plan of ghx_put_create reports its
+ * tiles as pair tiles and zeros for the transformed part. */
+int ghx_cs_put_create(const ghx_pack_entry* src, int32_t n_src, const ghx_pack_entry* dst,
+                      int32_t n_dst, const ghx_cs_item* dst_cs, const ghx_box* const* dst_global,
+                      const int32_t* const* dst_tiles, ghx_put** out);
+int ghx_cs_put_info(const ghx_put* put, int32_t* n_pair_tiles, int32_t* n_x_records,
+                    int32_t* n_x_tiles);
 
 /* Device-side access epochs of the zero-copy exchanges (bulk puts, direct pack): the reference's
  * access guards (include/ghex/rma/access_guard.hpp:35-140; per range: start/end_target_epoch on
