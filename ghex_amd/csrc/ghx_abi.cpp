@@ -499,6 +499,69 @@ void build_mixed(exchange_plan& ex, int32_t me, const std::vector<ghx_pack_entry
     ex.mixed = true;
 }
 
+// One receive (target) space against the send (source) space at the same message bytes, for
+// build_cs_self and build_cs_put. A space that cs_plan_space plans as ordinary segments which the
+// sender's add_box_segments match one to one pairs: `from` / `to` hold segment k of each side over
+// the same bytes, slots unset. Every other space becomes `box`: the receiving side's dense box
+// (field slot re.field_slot, buffer slot `buf_slot`) with the sending side of the same cells.
+// Throws `invalid` with the reason for what neither form can serve.
+struct cs_pairing
+{
+    bool paired = false;
+    std::vector<seg_s> from, to;
+    xsbox box{};
+    uint64_t bytes = 0;  // the space's message bytes
+};
+cs_pairing pair_cs_space(const ghx_pack_entry& se, const ghx_box& sbox, const ghx_pack_entry& re,
+                         const ghx_cs_item& item, const is_pair& space, int32_t tile,
+                         int32_t buf_slot, uint64_t off)
+{
+    const ghx_field_desc& fs = se.field;
+    const ghx_field_desc& fr = re.field;
+    bool same = fs.elem_size == fr.elem_size && fs.dim == fr.dim &&
+                fs.has_components == fr.has_components && fs.num_components == fr.num_components;
+    for (int d = 0; same && d < fr.dim; ++d) same = fs.layout[d] == fr.layout[d];
+    if (!same)
+        throw invalid("the two fields of a message differ in element size, components or "
+                      "layout order (the message's axis order differs between the two sides)");
+    cs_pairing pr;
+    cs_recv_plan rp;
+    cs_plan_space(rp, fr, item, space, tile, re.field_slot, re.buffer_slot, off, &pr.bytes);
+    add_box_segments(pr.from, fs, sbox, 0, 0, off);  // also checks the source's bounds
+    pr.paired = rp.xs.empty() && pr.from.size() == rp.segs.size();
+    for (size_t i = 0; pr.paired && i < pr.from.size(); ++i)
+        pr.paired = exchange_plan::same_message(pr.from[i], rp.segs[i]);
+    if (pr.paired)
+    {
+        pr.to = rp.segs;
+        return pr;
+    }
+    pr.from.clear();
+    const int64_t elem = fr.elem_size;
+    if (elem > 16 || (elem & (elem - 1)))
+        throw invalid("a space that cannot be paired holds elements that are not 1, 2, 4, 8 or 16 bytes");
+    xsbox& x = pr.box;
+    x.dst = rp.xs.empty() ? cs_space_box(fr, item, space, tile, re.field_slot, buf_slot, off) : rp.xs[0];
+    // the sending side of the same dense box: its axes are the sender's dims in layout order,
+    // fastest first — the receiver's order, the layouts being equal
+    const int D = fs.dim;
+    int by_speed[GHX_MAX_DIM];
+    for (int d = 0; d < D; ++d) by_speed[D - 1 - fs.layout[d]] = d;
+    x.src_off = 0;
+    for (int d = 0; d < 3; ++d) x.src_off += (int64_t(sbox.first[d]) + fs.offsets[d]) * fs.byte_strides[d];
+    for (int a = 0; a < 4; ++a) x.src_stride[a] = 0;
+    for (int a = 0; a < D; ++a)
+    {
+        const int d = by_speed[a];
+        const int64_t ext = d < 3 ? int64_t(sbox.last[d]) - sbox.first[d] + 1 : int64_t(fs.num_components);
+        if (ext != int64_t(x.dst.ext[a]))
+            throw invalid("a source box and its target box differ in shape under the tile transform");
+        x.src_stride[a] = fs.byte_strides[d];
+    }
+    x.src_slot = se.field_slot;
+    return pr;
+}
+
 // The fused self exchange of a cubed-sphere exchange (cs_self_plan, k_self_cs), built device-less
 // with the exchange; left absent, with the reason in ex.cs_self_reason, when the exchange has a
 // message that leaves the rank, has more pointers than the launch's table, pairs fields of different
@@ -568,77 +631,32 @@ void build_cs_self(exchange_plan& ex, const ghx_cs_item* cs, int32_t me,
     {
         const ghx_pack_entry& re = rent[k];
         const halo_entry& he = *rhalos[k];
-        const ghx_field_desc& fr = re.field;
         uint64_t off = re.buffer_offset;
         for (size_t b = 0; b < he.boxes.size(); ++b)
         {
             const auto it = by_bytes.find({re.buffer_slot, off});
             if (it == by_bytes.end())
                 return refuse("a receive space has no send space at the same buffer bytes");
-            const ghx_pack_entry& se = *it->second.e;
-            const ghx_box& sbox = *it->second.box;
-            const ghx_field_desc& fs = se.field;
-            bool same = fs.elem_size == fr.elem_size && fs.dim == fr.dim &&
-                        fs.has_components == fr.has_components && fs.num_components == fr.num_components;
-            for (int d = 0; same && d < fr.dim; ++d) same = fs.layout[d] == fr.layout[d];
-            if (!same)
-                return refuse("paired fields differ in element size, components or layout order "
-                              "(the buffer's axis order differs between the two sides)");
-            cs_recv_plan rp;
-            uint64_t nb = 0;
-            cs_plan_space(rp, fr, cs[re.field_slot], he.boxes[b], he.tiles[b], re.field_slot,
-                          re.buffer_slot, off, &nb);
-            bool paired = rp.xs.empty();
-            std::vector<seg_s> ps;
-            if (paired)
+            cs_pairing pr;
+            try
             {
-                add_box_segments(ps, fs, sbox, 0, 0, off);
-                paired = ps.size() == rp.segs.size();
-                for (size_t i = 0; paired && i < ps.size(); ++i)
-                    paired = exchange_plan::same_message(ps[i], rp.segs[i]);
+                pr = pair_cs_space(*it->second.e, *it->second.box, re, cs[re.field_slot], he.boxes[b],
+                                   he.tiles[b], re.buffer_slot, off);
             }
-            if (paired)
+            catch (const invalid& e)
             {
-                for (size_t i = 0; i < ps.size(); ++i)
-                {
-                    pack.push_back(ps[i]);
-                    unpack.push_back(rp.segs[i]);
-                    gf_p.push_back(se.field_slot);
-                    gf_u.push_back(re.field_slot);
-                    gb.push_back(re.buffer_slot);
-                }
+                return refuse(e.what());
             }
-            else
+            for (size_t i = 0; i < pr.from.size(); ++i)
             {
-                const int64_t elem = fr.elem_size;
-                if (elem > 16 || (elem & (elem - 1)))
-                    return refuse("a space that cannot be paired holds elements that are not 1, 2, 4, 8 or 16 bytes");
-                xsbox x{};
-                x.dst = rp.xs.empty() ? cs_space_box(fr, cs[re.field_slot], he.boxes[b], he.tiles[b],
-                                                     re.field_slot, re.buffer_slot, off)
-                                      : rp.xs[0];
-                // the sending side of the same dense box: its axes are the sender's dims in
-                // layout order, fastest first — the receiver's order, the layouts being equal
-                const int D = fs.dim;
-                int by_speed[GHX_MAX_DIM];
-                for (int d = 0; d < D; ++d) by_speed[D - 1 - fs.layout[d]] = d;
-                x.src_off = 0;
-                for (int d = 0; d < 3; ++d)
-                    x.src_off += (int64_t(sbox.first[d]) + fs.offsets[d]) * fs.byte_strides[d];
-                for (int a = 0; a < 4; ++a) x.src_stride[a] = 0;
-                for (int a = 0; a < D; ++a)
-                {
-                    const int d = by_speed[a];
-                    const int64_t ext = d < 3 ? int64_t(sbox.last[d]) - sbox.first[d] + 1
-                                              : int64_t(fs.num_components);
-                    if (ext != int64_t(x.dst.ext[a]))
-                        return refuse("a send space and its receive space differ in shape");
-                    x.src_stride[a] = fs.byte_strides[d];
-                }
-                x.src_slot = se.field_slot;
-                boxes.push_back(x);
+                pack.push_back(pr.from[i]);
+                unpack.push_back(pr.to[i]);
+                gf_p.push_back(it->second.e->field_slot);
+                gf_u.push_back(re.field_slot);
+                gb.push_back(re.buffer_slot);
             }
-            off += nb;
+            if (!pr.paired) boxes.push_back(pr.box);
+            off += pr.bytes;
         }
     }
     try
@@ -660,8 +678,7 @@ int check_ptr(const void* p, const char* what)
 
 // The put plan of ghx_cs_put_create (cs_put_plan, k_put_cs): build_cs_self's pairing without the
 // buffer. Each target space (dst[k]'s box b with its global box and tile) is matched with the
-// source space at the same virtual message bytes; spaces cs_plan_space plans as ordinary segments
-// that the sender's add_box_segments match one to one become pair records, every other space put
+// source space at the same virtual message bytes and routed by pair_cs_space: pair records or put
 // tile records. Throws `invalid` with the reason for what a put cannot serve.
 std::unique_ptr<cs_put_plan> build_cs_put(const ghx_pack_entry* src, int n_src,
                                           const ghx_pack_entry* dst, int n_dst,
@@ -723,22 +740,12 @@ std::unique_ptr<cs_put_plan> build_cs_put(const ghx_pack_entry* src, int n_src,
         check_cs_item(re.field, cs[k]);
         if (re.n_boxes > 0 && (!global[k] || !tiles[k]))
             throw invalid("a target entry without the global boxes or tiles of its spaces");
-        const ghx_field_desc& fr = re.field;
         uint64_t off = re.buffer_offset;
         for (int b = 0; b < re.n_boxes; ++b, ++n_dst_spaces)
         {
             const auto it = by_bytes.find({re.buffer_slot, off});
             if (it == by_bytes.end())
                 throw invalid("a target space has no source space at the same message bytes");
-            const ghx_pack_entry& se = *it->second.e;
-            const ghx_box& sbox = *it->second.box;
-            const ghx_field_desc& fs = se.field;
-            bool same = fs.elem_size == fr.elem_size && fs.dim == fr.dim &&
-                        fs.has_components == fr.has_components && fs.num_components == fr.num_components;
-            for (int d = 0; same && d < fr.dim; ++d) same = fs.layout[d] == fr.layout[d];
-            if (!same)
-                throw invalid("the two fields of a message differ in element size, components or "
-                              "layout order (the message's axis order differs between the two sides)");
             is_pair sp{};
             for (int d = 0; d < 3; ++d)
             {
@@ -749,58 +756,21 @@ std::unique_ptr<cs_put_plan> build_cs_put(const ghx_pack_entry* src, int n_src,
             }
             // the message is the dense box in the sender's coordinates, which are the global
             // box's: the source box must have its shape (the target's under the transform)
+            const ghx_box& sbox = *it->second.box;
             for (int d = 0; d < 3; ++d)
                 if (int64_t(sbox.last[d]) - sbox.first[d] != int64_t(sp.gl[d]) - sp.gf[d])
                     throw invalid("a source box and its target box differ in shape under the tile transform");
-            cs_recv_plan rp;
-            uint64_t nb = 0;
-            cs_plan_space(rp, fr, cs[k], sp, tiles[k][b], re.field_slot, re.buffer_slot, off, &nb);
-            std::vector<seg_s> ps;
-            add_box_segments(ps, fs, sbox, 0, 0, off);  // also checks the source's bounds
-            bool paired = rp.xs.empty() && ps.size() == rp.segs.size();
-            for (size_t i = 0; paired && i < ps.size(); ++i)
-                paired = exchange_plan::same_message(ps[i], rp.segs[i]);
-            if (paired)
+            const cs_pairing pr = pair_cs_space(*it->second.e, sbox, re, cs[k], sp, tiles[k][b], 0, off);
+            for (size_t i = 0; i < pr.from.size(); ++i)
             {
-                for (size_t i = 0; i < ps.size(); ++i)
-                {
-                    from.push_back(ps[i]);
-                    to.push_back(rp.segs[i]);
-                    gs.push_back(se.field_slot);
-                    gd.push_back(re.field_slot);
-                }
+                from.push_back(pr.from[i]);
+                to.push_back(pr.to[i]);
+                gs.push_back(it->second.e->field_slot);
+                gd.push_back(re.field_slot);
             }
-            else
-            {
-                const int64_t elem = fr.elem_size;
-                if (elem > 16 || (elem & (elem - 1)))
-                    throw invalid("a space that cannot be paired holds elements that are not 1, 2, 4, 8 or 16 bytes");
-                xsbox x{};
-                x.dst = rp.xs.empty() ? cs_space_box(fr, cs[k], sp, tiles[k][b], re.field_slot, 0, off)
-                                      : rp.xs[0];
-                // the sending side of the same dense box: its axes are the sender's dims in
-                // layout order, fastest first — the receiver's order, the layouts being equal
-                const int D = fs.dim;
-                int by_speed[GHX_MAX_DIM];
-                for (int d = 0; d < D; ++d) by_speed[D - 1 - fs.layout[d]] = d;
-                x.src_off = 0;
-                for (int d = 0; d < 3; ++d)
-                    x.src_off += (int64_t(sbox.first[d]) + fs.offsets[d]) * fs.byte_strides[d];
-                for (int a = 0; a < 4; ++a) x.src_stride[a] = 0;
-                for (int a = 0; a < D; ++a)
-                {
-                    const int d = by_speed[a];
-                    const int64_t ext = d < 3 ? int64_t(sbox.last[d]) - sbox.first[d] + 1
-                                              : int64_t(fs.num_components);
-                    if (ext != int64_t(x.dst.ext[a]))
-                        throw invalid("a source box and its target box differ in shape under the tile transform");
-                    x.src_stride[a] = fs.byte_strides[d];
-                }
-                x.src_slot = se.field_slot;
-                boxes.push_back(x);
-            }
-            bytes += nb;
-            off += nb;
+            if (!pr.paired) boxes.push_back(pr.box);
+            bytes += pr.bytes;
+            off += pr.bytes;
         }
     }
     if (n_dst_spaces != n_src_spaces)

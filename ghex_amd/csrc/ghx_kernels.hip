@@ -25,6 +25,7 @@
 #include <utility>
 #include <vector>
 
+#include "ghx_addr.hpp"
 #include "ghx_internal.hpp"
 
 namespace ghx
@@ -57,12 +58,6 @@ static void launch(K kernel, uint32_t grid, hipStream_t s, A... args)
 namespace
 {
 constexpr int kU = 4;  // vectors in flight per lane per loop trip
-
-__device__ __forceinline__ uint32_t fastdiv(uint32_t n, magic_u32 m)
-{
-    const uint32_t t = __umulhi(m.m, n);
-    return (t + ((n - t) >> m.s1)) >> m.s2;
-}
 
 template<int W>
 struct vec_t;
@@ -148,21 +143,6 @@ __device__ __forceinline__ void fstore(char* p, V v, uint32_t pol)
         }
     }
     vstore<V>(p, v);
-}
-
-// field byte offset of segment-relative buffer position p (structured)
-__device__ __forceinline__ int64_t field_offset_s(const seg_s& s, uint32_t p)
-{
-    const uint32_t row = fastdiv(p, s.mag_row);
-    const uint32_t col = p - row * s.row_bytes;
-    const uint32_t q0 = fastdiv(row, s.mag_ext[0]);
-    const uint32_t c0 = row - q0 * s.ext[0];
-    const uint32_t q1 = fastdiv(q0, s.mag_ext[1]);
-    const uint32_t c1 = q0 - q1 * s.ext[1];
-    const uint32_t q2 = fastdiv(q1, s.mag_ext[2]);
-    const uint32_t c2 = q1 - q2 * s.ext[2];
-    return s.field_off + int64_t(c0) * s.stride[0] + int64_t(c1) * s.stride[1] +
-           int64_t(c2) * s.stride[2] + int64_t(q2) * s.stride[3] + int64_t(col);
 }
 
 // The short form (seg_s::amode 1 / 2, planner short_addressing): the offset of buffer position
@@ -750,12 +730,55 @@ __device__ __forceinline__ void self_forward(const seg_s& s, const seg_s& q,
     }
 }
 
-// Fused self exchange: every message is a self message, so pack segment k and unpack segment k
-// cover the same buffer bytes with the same tiling. When both halves of a tile use the same
+// One tile of a fused self exchange (k_self, k_self_cs): pack segment s and unpack segment q
+// cover the same buffer bytes with the same tiling. When both halves of the tile use the same
 // vector width (always, for aligned fields) every lane unpacks exactly the bytes it packed:
 // it writes the halo from the registers it stored the buffer from (self_forward), no barrier.
 // Otherwise the workgroup packs its tile (field interior -> buffer), passes a workgroup barrier
 // (its own stores are visible to its own waves), then unpacks the same bytes (buffer -> halo).
+// PEERS: q.bytes == 0 marks a peer message of a mixed exchange (ghx_exchange_pack_self), which
+// is packed only.
+template<bool PEERS>
+__device__ __forceinline__ void self_pair_tile(const seg_s& s, const seg_s& q, uint32_t ti,
+                                               char* field_p, char* field_u, char* buf)
+{
+    const uint32_t start = ti * s.tile_bytes;
+    const uint32_t end = min(start + s.tile_bytes, s.bytes);
+    int wp = min(int(s.wlog2), ptr_wlog2(reinterpret_cast<uint64_t>(field_p)));
+    wp = min(wp, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
+    int wu = min(int(q.wlog2), ptr_wlog2(reinterpret_cast<uint64_t>(field_u)));
+    wu = min(wu, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
+    if constexpr (PEERS)
+        if (q.bytes == 0)
+        {
+            copy_any<true, kU>(s, field_p, buf, start, end, wp);
+            return;
+        }
+    if (wp == wu && s.amode == 1 && q.amode == 1 && wp >= 3)
+    {
+        if (wp == 4) self_forward<16, 1>(s, q, field_p, field_u, buf, start, end);
+        else self_forward<8, 1>(s, q, field_p, field_u, buf, start, end);
+        return;
+    }
+    if (wp == wu)
+    {
+        switch (wp)
+        {
+            case 4: self_forward<16>(s, q, field_p, field_u, buf, start, end); break;
+            case 3: self_forward<8>(s, q, field_p, field_u, buf, start, end); break;
+            case 2: self_forward<4>(s, q, field_p, field_u, buf, start, end); break;
+            case 1: self_forward<2>(s, q, field_p, field_u, buf, start, end); break;
+            default: self_forward<1>(s, q, field_p, field_u, buf, start, end); break;
+        }
+        return;
+    }
+    copy_any<true, kU>(s, field_p, buf, start, end, wp);
+    __syncthreads();  // workgroup release/acquire: the tile's buffer bytes are complete
+    copy_any<false, kU>(q, field_u, buf, start, end, wu);
+    __syncthreads();  // the next tile of a grid-stride loop reuses the lanes
+}
+
+// Fused self exchange: every message is a self message (or, mixed, a peer message to pack).
 // REC: pair records (upload_pair_records) — the workgroup loads its tile's pack and unpack
 // segments side by side at tile_recs[2 * blockIdx.x], no tile-table load ahead of them.
 template<bool DBL = false, bool REC = false>
@@ -783,45 +806,12 @@ __global__ __launch_bounds__(kBlock) void k_self(kargs a)
             s = ps[si];
             q = us[si];
         }
-        const uint32_t start = ti * s.tile_bytes;
-        const uint32_t end = min(start + s.tile_bytes, s.bytes);
         char* field_p = reinterpret_cast<char*>(a.field_ptr[s.field_slot]);
         char* field_u = reinterpret_cast<char*>(a.field_ptr[q.field_slot]);
         char* buf = reinterpret_cast<char*>(a.buf_ptr[s.buf_slot]) + s.buf_off;
         if constexpr (DBL)
             if (odd) buf += a.dbl_off[s.buf_slot];
-        int wp = min(int(s.wlog2), ptr_wlog2(reinterpret_cast<uint64_t>(field_p)));
-        wp = min(wp, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
-        int wu = min(int(q.wlog2), ptr_wlog2(reinterpret_cast<uint64_t>(field_u)));
-        wu = min(wu, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
-        if (q.bytes == 0)
-        {
-            // a peer message of a mixed exchange (ghx_exchange_pack_self): pack only
-            copy_any<true, kU>(s, field_p, buf, start, end, wp);
-            continue;
-        }
-        if (wp == wu && s.amode == 1 && q.amode == 1 && wp >= 3)
-        {
-            if (wp == 4) self_forward<16, 1>(s, q, field_p, field_u, buf, start, end);
-            else self_forward<8, 1>(s, q, field_p, field_u, buf, start, end);
-            continue;
-        }
-        if (wp == wu)
-        {
-            switch (wp)
-            {
-                case 4: self_forward<16>(s, q, field_p, field_u, buf, start, end); break;
-                case 3: self_forward<8>(s, q, field_p, field_u, buf, start, end); break;
-                case 2: self_forward<4>(s, q, field_p, field_u, buf, start, end); break;
-                case 1: self_forward<2>(s, q, field_p, field_u, buf, start, end); break;
-                default: self_forward<1>(s, q, field_p, field_u, buf, start, end); break;
-            }
-            continue;
-        }
-        copy_any<true, kU>(s, field_p, buf, start, end, wp);
-        __syncthreads();  // workgroup release/acquire: the tile's buffer bytes are complete
-        copy_any<false, kU>(q, field_u, buf, start, end, wu);
-        __syncthreads();  // the next tile of a grid-stride loop reuses the lanes
+        self_pair_tile<true>(s, q, ti, field_p, field_u, buf);
     }
 }
 
@@ -871,6 +861,31 @@ __device__ __forceinline__ void copy_direct(const seg_s& s, const seg_s& q,
     }
 }
 
+// One tile of a put (k_put, k_put_cs) at the widest vector both segments and both pointers allow.
+__device__ __forceinline__ void put_pair_tile(const seg_s& s, const seg_s& q, uint32_t ti,
+                                              const char* src, char* dst)
+{
+    const uint32_t start = ti * s.tile_bytes;
+    const uint32_t end = min(start + s.tile_bytes, s.bytes);
+    int w = min(int(s.wlog2), int(q.wlog2));
+    w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(src)));
+    w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(dst)));
+    if (s.amode == 1 && q.amode == 1 && w >= 3)
+    {
+        if (w == 4) copy_direct<16, 1>(s, q, src, dst, start, end);
+        else copy_direct<8, 1>(s, q, src, dst, start, end);
+        return;
+    }
+    switch (w)
+    {
+        case 4: copy_direct<16>(s, q, src, dst, start, end); break;
+        case 3: copy_direct<8>(s, q, src, dst, start, end); break;
+        case 2: copy_direct<4>(s, q, src, dst, start, end); break;
+        case 1: copy_direct<2>(s, q, src, dst, start, end); break;
+        default: copy_direct<1>(s, q, src, dst, start, end); break;
+    }
+}
+
 template<bool REC = false>
 __global__ __launch_bounds__(kBlock) void k_put(kargs a)
 {
@@ -894,212 +909,156 @@ __global__ __launch_bounds__(kBlock) void k_put(kargs a)
             s = ps[si];
             q = qs[si];
         }
-        const uint32_t start = ti * s.tile_bytes;
-        const uint32_t end = min(start + s.tile_bytes, s.bytes);
-        const char* src = reinterpret_cast<const char*>(a.field_ptr[s.field_slot]);
-        char* dst = reinterpret_cast<char*>(a.buf_ptr[q.field_slot]);
-        int w = min(int(s.wlog2), int(q.wlog2));
-        w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(src)));
-        w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(dst)));
-        if (s.amode == 1 && q.amode == 1 && w >= 3)
-        {
-            if (w == 4) copy_direct<16, 1>(s, q, src, dst, start, end);
-            else copy_direct<8, 1>(s, q, src, dst, start, end);
-            continue;
-        }
-        switch (w)
-        {
-            case 4: copy_direct<16>(s, q, src, dst, start, end); break;
-            case 3: copy_direct<8>(s, q, src, dst, start, end); break;
-            case 2: copy_direct<4>(s, q, src, dst, start, end); break;
-            case 1: copy_direct<2>(s, q, src, dst, start, end); break;
-            default: copy_direct<1>(s, q, src, dst, start, end); break;
-        }
+        put_pair_tile(s, q, ti, reinterpret_cast<const char*>(a.field_ptr[s.field_slot]),
+                      reinterpret_cast<char*>(a.buf_ptr[q.field_slot]));
     }
 }
 
-// Transformed unpack (cubed sphere): one workgroup per tile record (seg_x).
-//
-// The tile is a sub-box of the buffer's dense box (the halo in the neighbour tile's
-// coordinates), about one element per lane, walked in FIELD order: the record's axes are sorted
-// by ascending |field stride|, so consecutive lanes write consecutive field elements of one run
-// and a wave's store covers whole runs, while its loads fall on a few long pieces of buffer rows
-// (for an x-stride-1 field and a halo of width H rotated by 90 degrees: H buffer rows of up to
-// 256 / H elements each, written as H-element field runs, where the element-row form of the
-// ordinary kernel issues one store per line). A reversed axis is a negative stride. Vector
-// components are negated in registers between the load and the store
-// (cubed_sphere/field_descriptor.hpp:97-104): sign-bit flip (neg_kind 1) or two's-complement
-// negate (2) of component 0 / 1 by neg_mask. Staging the tile through LDS (buffer range read
-// lane-linear, transposed reads from LDS) measured slower at every tile size: the launch is
-// latency-bound and the LDS round trip and its barrier sit in the dependent chain.
+// An element of 2^E bytes: element-wide when `aligned`, else byte by byte (a buffer or field
+// whose base or strides are not multiples of the element size).
 template<int E>
-__device__ __forceinline__ void unpack_x_tile(const seg_x& s, const char* __restrict__ src,
-                                              char* __restrict__ field, bool aligned)
+__device__ __forceinline__ typename vec_t<(1 << E)>::type load_elem(const char* p, bool aligned)
 {
     using V = typename vec_t<(1 << E)>::type;
+    if (aligned) return vload<V>(p);
+    unsigned char b[1 << E];
+#pragma unroll
+    for (int k = 0; k < (1 << E); ++k) b[k] = vload<unsigned char>(p + k);
+    V v;
+    __builtin_memcpy(&v, b, sizeof(V));
+    return v;
+}
+
+template<int E>
+__device__ __forceinline__ void store_elem(char* p, typename vec_t<(1 << E)>::type v, bool aligned)
+{
+    using V = typename vec_t<(1 << E)>::type;
+    if (aligned)
+    {
+        vstore<V>(p, v);
+        return;
+    }
+    unsigned char b[1 << E];
+    __builtin_memcpy(b, &v, sizeof(V));
+#pragma unroll
+    for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(p + k, b[k]);
+}
+
+// Negation of a vector component (cubed_sphere/field_descriptor.hpp:97-104): sign-bit flip
+// (kind 1) or two's-complement negate (2) of a 4- or 8-byte element; other widths are opaque.
+template<int E>
+__device__ __forceinline__ typename vec_t<(1 << E)>::type negate_elem(
+    typename vec_t<(1 << E)>::type v, uint32_t kind)
+{
+    if constexpr (E == 2)
+        v = kind == 1 ? (v ^ 0x80000000u) : (0u - v);
+    else if constexpr (E == 3)
+    {
+        if (kind == 1) v.y ^= 0x80000000u;
+        else
+        {
+            const uint64_t w = 0ull - ((uint64_t(v.y) << 32) | v.x);
+            v.x = uint32_t(w);
+            v.y = uint32_t(w >> 32);
+        }
+    }
+    return v;
+}
+
+// The transformed tile walk (cubed sphere) of k_unpack_x, k_self_cs and k_put_cs:
+// one workgroup per tile record, one element per lane.
+//
+// The tile is a sub-box of the message's dense box (the halo in the neighbour tile's
+// coordinates), walked in FIELD order: the record's axes are sorted by ascending |stride| of the
+// RECEIVING field, so consecutive lanes write consecutive field elements of one run and a wave's
+// store covers whole runs (the side that may cross xGMI in a put), while its loads fall on a few
+// long pieces of buffer rows or of the sending field's rows (for an x-stride-1 field and a halo
+// of width H rotated by 90 degrees: H rows of up to 256 / H elements each, written as H-element
+// field runs, where the element-row form of the ordinary kernel issues one store per line). A
+// reversed axis is a negative stride. Vector components are negated in registers between the
+// load and the store to the field. No LDS: staging the tile through LDS (buffer range read
+// lane-linear, transposed reads from LDS) measured slower at every tile size: the launch is
+// latency-bound and the LDS round trip and its barrier sit in the dependent chain. No barrier
+// and no ordering among workgroups either: the planner has checked that no cell a launch reads
+// is a cell it writes (it refuses source boxes that reach into the sender's halo). Plain global
+// stores only: the destination may be a peer's mapped memory, and the epochs' system-scope
+// release at close covers nothing else.
+// FROM_FIELD: the element comes from the sending field (r->src_*), not from its buffer cell.
+// TO_CELL: it is also stored, as loaded, to its buffer cell.
+template<int E, bool FROM_FIELD, bool TO_CELL>
+__device__ __forceinline__ void walk_x_tile(const seg_x& s, const seg_xs* r,
+                                            const char* __restrict__ send, char* __restrict__ cells,
+                                            char* __restrict__ field, bool aligned)
+{
     const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
     for (uint32_t i = threadIdx.x; i < total; i += kBlock)
     {
-        const uint32_t q0 = fastdiv(i, s.mag[0]);
-        const uint32_t c0 = i - q0 * s.tdim[0];
-        const uint32_t q1 = fastdiv(q0, s.mag[1]);
-        const uint32_t c1 = q0 - q1 * s.tdim[1];
-        const uint32_t c3 = fastdiv(q1, s.mag[2]);
-        const uint32_t c2 = q1 - c3 * s.tdim[2];
-        if (c0 >= s.act[0] || c1 >= s.act[1] || c2 >= s.act[2] || c3 >= s.act[3]) continue;
-        const uint32_t bi = c0 * s.bstride[0] + c1 * s.bstride[1] + c2 * s.bstride[2] +
-                            c3 * s.bstride[3];
-        const char* from = src + (size_t(bi) << E);
-        V v;
-        if (aligned) v = vload<V>(from);
-        else
+        uint32_t c[4];
+        if (!tile_decode(s, i, c)) continue;
+        char* cell = nullptr;
+        if constexpr (!FROM_FIELD || TO_CELL) cell = cells + (size_t(tile_cell(s, c)) << E);
+        const char* from = cell;
+        if constexpr (FROM_FIELD) from = affine_offset(send + r->src_off, r->src_stride, c);
+        const auto v = load_elem<E>(from, aligned);
+        auto w = v;
+        if (s.neg_mask)  // uniform per tile: most tiles negate nothing
         {
-            // a buffer or field whose base or strides are not multiples of the element size
-            unsigned char b[1 << E];
-#pragma unroll
-            for (int k = 0; k < (1 << E); ++k) b[k] = vload<unsigned char>(from + k);
-            __builtin_memcpy(&v, b, sizeof(V));
+            if (tile_negates(s, c)) w = negate_elem<E>(v, s.neg_kind);
         }
-        if (s.neg_mask)
-        {
-            uint32_t comp = s.comp0;
-            if (s.comp_pos < 4) comp += s.comp_pos == 0 ? c0 : s.comp_pos == 1 ? c1 : s.comp_pos == 2 ? c2 : c3;
-            if (comp < 2 && ((s.neg_mask >> comp) & 1u))
-            {
-                if constexpr (E == 2)
-                    v = s.neg_kind == 1 ? (v ^ 0x80000000u) : (0u - v);
-                else if constexpr (E == 3)
-                {
-                    if (s.neg_kind == 1) v.y ^= 0x80000000u;
-                    else
-                    {
-                        const uint64_t w = 0ull - ((uint64_t(v.y) << 32) | v.x);
-                        v.x = uint32_t(w);
-                        v.y = uint32_t(w >> 32);
-                    }
-                }
-            }
-        }
-        char* dst = field + s.field_off + int64_t(c0) * s.stride[0] + int64_t(c1) * s.stride[1] +
-                    int64_t(c2) * s.stride[2] + int64_t(c3) * s.stride[3];
-        if (aligned) vstore<V>(dst, v);
-        else
-        {
-            unsigned char b[1 << E];
-            __builtin_memcpy(b, &v, sizeof(V));
-#pragma unroll
-            for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(dst + k, b[k]);
-        }
+        // both stores after the negation: nothing then waits between them for the first to land
+        if constexpr (TO_CELL) store_elem<E>(cell, v, aligned);
+        store_elem<E>(affine_offset(field + s.field_off, s.stride, c), w, aligned);
     }
 }
 
+// The walk at the record's element width. Element-wide accesses when the source, the buffer
+// (where the form uses it), the destination and every stride used are element-aligned (uniform
+// per tile; a mapped peer pointer's alignment is a run-time fact).
+template<bool FROM_FIELD, bool TO_CELL>
+__device__ __forceinline__ void walk_x(const seg_x& s, const seg_xs* r, const char* send,
+                                       char* cells, char* field)
+{
+    const uint64_t em = (1u << s.elog2) - 1u;
+    uint64_t strides = uint64_t(s.stride[0]) | uint64_t(s.stride[1]) | uint64_t(s.stride[2]) |
+                       uint64_t(s.stride[3]);
+    bool aligned = true;
+    if constexpr (FROM_FIELD)
+    {
+        aligned = ((reinterpret_cast<uint64_t>(send) + uint64_t(r->src_off)) & em) == 0;
+        strides |= uint64_t(r->src_stride[0]) | uint64_t(r->src_stride[1]) |
+                   uint64_t(r->src_stride[2]) | uint64_t(r->src_stride[3]);
+    }
+    if constexpr (!FROM_FIELD || TO_CELL) aligned = aligned && (reinterpret_cast<uint64_t>(cells) & em) == 0;
+    aligned = aligned && ((reinterpret_cast<uint64_t>(field) + uint64_t(s.field_off)) & em) == 0 &&
+              (strides & em) == 0;
+    switch (s.elog2)
+    {
+        case 4: walk_x_tile<4, FROM_FIELD, TO_CELL>(s, r, send, cells, field, aligned); break;
+        case 3: walk_x_tile<3, FROM_FIELD, TO_CELL>(s, r, send, cells, field, aligned); break;
+        case 2: walk_x_tile<2, FROM_FIELD, TO_CELL>(s, r, send, cells, field, aligned); break;
+        case 1: walk_x_tile<1, FROM_FIELD, TO_CELL>(s, r, send, cells, field, aligned); break;
+        default: walk_x_tile<0, FROM_FIELD, TO_CELL>(s, r, send, cells, field, aligned); break;
+    }
+}
+
+// Transformed unpack: buffer cell -> receiving field, one workgroup per seg_x record.
 __global__ __launch_bounds__(kBlock) void k_unpack_x(kargs a)
 {
     const seg_x* __restrict__ recs = static_cast<const seg_x*>(a.tile_recs);
     for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x)
     {
         const seg_x s = recs[t];
-        const char* src = reinterpret_cast<const char*>(a.buf_ptr[s.buf_slot]) + s.buf_off;
-        char* field = reinterpret_cast<char*>(a.field_ptr[s.field_slot]);
-        // element-wide accesses when both sides are element-aligned (uniform per tile)
-        const uint64_t em = (1u << s.elog2) - 1u;
-        const bool aligned =
-            (reinterpret_cast<uint64_t>(src) & em) == 0 &&
-            ((reinterpret_cast<uint64_t>(field) + uint64_t(s.field_off)) & em) == 0 &&
-            ((uint64_t(s.stride[0]) | uint64_t(s.stride[1]) | uint64_t(s.stride[2]) |
-              uint64_t(s.stride[3])) & em) == 0;
-        switch (s.elog2)
-        {
-            case 4: unpack_x_tile<4>(s, src, field, aligned); break;
-            case 3: unpack_x_tile<3>(s, src, field, aligned); break;
-            case 2: unpack_x_tile<2>(s, src, field, aligned); break;
-            case 1: unpack_x_tile<1>(s, src, field, aligned); break;
-            default: unpack_x_tile<0>(s, src, field, aligned); break;
-        }
+        walk_x<false, false>(s, nullptr, nullptr,
+                             reinterpret_cast<char*>(a.buf_ptr[s.buf_slot]) + s.buf_off,
+                             reinterpret_cast<char*>(a.field_ptr[s.field_slot]));
     }
 }
 
-// Fused cubed-sphere self exchange: pack and rotating unpack of an exchange
-// whose every message stays on this device, in ONE launch. Blocks [0, n_pair_tiles) take a pair
-// record and do what k_self's record form does with it (spaces whose pack and unpack segments
-// cover the same bytes with the same rows); the blocks after them take a self tile record
-// (seg_xs): each lane loads ONE element from the sending field, stores it as it is to its cell of
-// the buffer's dense box (the send buffers hold the packed message afterwards) and, negated in
-// registers as unpack_x_tile negates, to the receiving field. No buffer read-back, no LDS. The
-// planner has checked that no cell the launch reads is a cell it writes, so workgroups need no
-// ordering among themselves.
-template<int E>
-__device__ __forceinline__ void self_x_tile(const seg_xs& r, const char* __restrict__ src,
-                                            char* __restrict__ buf, char* __restrict__ field,
-                                            bool aligned)
-{
-    using V = typename vec_t<(1 << E)>::type;
-    const seg_x& s = r.x;
-    const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
-    for (uint32_t i = threadIdx.x; i < total; i += kBlock)
-    {
-        const uint32_t q0 = fastdiv(i, s.mag[0]);
-        const uint32_t c0 = i - q0 * s.tdim[0];
-        const uint32_t q1 = fastdiv(q0, s.mag[1]);
-        const uint32_t c1 = q0 - q1 * s.tdim[1];
-        const uint32_t c3 = fastdiv(q1, s.mag[2]);
-        const uint32_t c2 = q1 - c3 * s.tdim[2];
-        if (c0 >= s.act[0] || c1 >= s.act[1] || c2 >= s.act[2] || c3 >= s.act[3]) continue;
-        const char* from = src + r.src_off + int64_t(c0) * r.src_stride[0] +
-                           int64_t(c1) * r.src_stride[1] + int64_t(c2) * r.src_stride[2] +
-                           int64_t(c3) * r.src_stride[3];
-        const uint32_t bi = c0 * s.bstride[0] + c1 * s.bstride[1] + c2 * s.bstride[2] +
-                            c3 * s.bstride[3];
-        char* cell = buf + (size_t(bi) << E);
-        V v;
-        if (aligned)
-        {
-            v = vload<V>(from);
-            vstore<V>(cell, v);
-        }
-        else
-        {
-            // a field or buffer whose base or strides are not multiples of the element size
-            unsigned char b[1 << E];
-#pragma unroll
-            for (int k = 0; k < (1 << E); ++k) b[k] = vload<unsigned char>(from + k);
-#pragma unroll
-            for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(cell + k, b[k]);
-            __builtin_memcpy(&v, b, sizeof(V));
-        }
-        if (s.neg_mask)
-        {
-            uint32_t comp = s.comp0;
-            if (s.comp_pos < 4) comp += s.comp_pos == 0 ? c0 : s.comp_pos == 1 ? c1 : s.comp_pos == 2 ? c2 : c3;
-            if (comp < 2 && ((s.neg_mask >> comp) & 1u))
-            {
-                if constexpr (E == 2)
-                    v = s.neg_kind == 1 ? (v ^ 0x80000000u) : (0u - v);
-                else if constexpr (E == 3)
-                {
-                    if (s.neg_kind == 1) v.y ^= 0x80000000u;
-                    else
-                    {
-                        const uint64_t w = 0ull - ((uint64_t(v.y) << 32) | v.x);
-                        v.x = uint32_t(w);
-                        v.y = uint32_t(w >> 32);
-                    }
-                }
-            }
-        }
-        char* dst = field + s.field_off + int64_t(c0) * s.stride[0] + int64_t(c1) * s.stride[1] +
-                    int64_t(c2) * s.stride[2] + int64_t(c3) * s.stride[3];
-        if (aligned) vstore<V>(dst, v);
-        else
-        {
-            unsigned char b[1 << E];
-            __builtin_memcpy(b, &v, sizeof(V));
-#pragma unroll
-            for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(dst + k, b[k]);
-        }
-    }
-}
-
+// Fused cubed-sphere self exchange: pack and rotating unpack of an exchange whose every message
+// stays on this device, in ONE launch. Blocks [0, n_pair_tiles) take a pair record as k_self's
+// record form does (spaces whose pack and unpack segments cover the same bytes with the same
+// rows); the blocks after them take a self tile record (seg_xs): sending field -> buffer cell
+// (the send buffers hold the packed message afterwards) and receiving field, no buffer read-back.
 __global__ __launch_bounds__(kBlock) void k_self_cs(kargs_cs a)
 {
     const seg_s* __restrict__ pairs = static_cast<const seg_s*>(a.pair_recs);
@@ -1111,136 +1070,23 @@ __global__ __launch_bounds__(kBlock) void k_self_cs(kargs_cs a)
         {
             const seg_s s = pairs[2 * t];
             const seg_s q = pairs[2 * t + 1];
-            const uint32_t start = s.first_tile * s.tile_bytes;
-            const uint32_t end = min(start + s.tile_bytes, s.bytes);
-            char* field_p = reinterpret_cast<char*>(a.ptr[s.field_slot]);
-            char* field_u = reinterpret_cast<char*>(a.ptr[q.field_slot]);
-            char* buf = reinterpret_cast<char*>(a.ptr[a.buf_base + s.buf_slot]) + s.buf_off;
-            int wp = min(int(s.wlog2), ptr_wlog2(reinterpret_cast<uint64_t>(field_p)));
-            wp = min(wp, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
-            int wu = min(int(q.wlog2), ptr_wlog2(reinterpret_cast<uint64_t>(field_u)));
-            wu = min(wu, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
-            if (wp == wu && s.amode == 1 && q.amode == 1 && wp >= 3)
-            {
-                if (wp == 4) self_forward<16, 1>(s, q, field_p, field_u, buf, start, end);
-                else self_forward<8, 1>(s, q, field_p, field_u, buf, start, end);
-                continue;
-            }
-            if (wp == wu)
-            {
-                switch (wp)
-                {
-                    case 4: self_forward<16>(s, q, field_p, field_u, buf, start, end); break;
-                    case 3: self_forward<8>(s, q, field_p, field_u, buf, start, end); break;
-                    case 2: self_forward<4>(s, q, field_p, field_u, buf, start, end); break;
-                    case 1: self_forward<2>(s, q, field_p, field_u, buf, start, end); break;
-                    default: self_forward<1>(s, q, field_p, field_u, buf, start, end); break;
-                }
-                continue;
-            }
-            copy_any<true, kU>(s, field_p, buf, start, end, wp);
-            __syncthreads();  // workgroup release/acquire: the tile's buffer bytes are complete
-            copy_any<false, kU>(q, field_u, buf, start, end, wu);
-            __syncthreads();  // the next tile of a grid-stride loop reuses the lanes
+            self_pair_tile<false>(s, q, s.first_tile, reinterpret_cast<char*>(a.ptr[s.field_slot]),
+                                  reinterpret_cast<char*>(a.ptr[q.field_slot]),
+                                  reinterpret_cast<char*>(a.ptr[a.buf_base + s.buf_slot]) + s.buf_off);
             continue;
         }
         const seg_xs r = xrecs[t - a.n_pair_tiles];
-        const char* src = reinterpret_cast<const char*>(a.ptr[r.src_slot]);
-        char* buf = reinterpret_cast<char*>(a.ptr[a.buf_base + r.x.buf_slot]) + r.x.buf_off;
-        char* field = reinterpret_cast<char*>(a.ptr[r.x.field_slot]);
-        // element-wide accesses when the source, the buffer, the destination and every stride
-        // are element-aligned (uniform per tile)
-        const uint64_t em = (1u << r.x.elog2) - 1u;
-        const bool aligned =
-            ((reinterpret_cast<uint64_t>(src) + uint64_t(r.src_off)) & em) == 0 &&
-            (reinterpret_cast<uint64_t>(buf) & em) == 0 &&
-            ((reinterpret_cast<uint64_t>(field) + uint64_t(r.x.field_off)) & em) == 0 &&
-            ((uint64_t(r.x.stride[0]) | uint64_t(r.x.stride[1]) | uint64_t(r.x.stride[2]) |
-              uint64_t(r.x.stride[3]) | uint64_t(r.src_stride[0]) | uint64_t(r.src_stride[1]) |
-              uint64_t(r.src_stride[2]) | uint64_t(r.src_stride[3])) & em) == 0;
-        switch (r.x.elog2)
-        {
-            case 4: self_x_tile<4>(r, src, buf, field, aligned); break;
-            case 3: self_x_tile<3>(r, src, buf, field, aligned); break;
-            case 2: self_x_tile<2>(r, src, buf, field, aligned); break;
-            case 1: self_x_tile<1>(r, src, buf, field, aligned); break;
-            default: self_x_tile<0>(r, src, buf, field, aligned); break;
-        }
+        walk_x<true, true>(r.x, &r, reinterpret_cast<const char*>(a.ptr[r.src_slot]),
+                           reinterpret_cast<char*>(a.ptr[a.buf_base + r.x.buf_slot]) + r.x.buf_off,
+                           reinterpret_cast<char*>(a.ptr[r.x.field_slot]));
     }
 }
 
-// Cubed-sphere put: k_self_cs's walk without the buffer, the destination being
-// any mapped field (this device's or a node-local peer's through IPC). Blocks [0, n_pair_tiles)
-// take a pair record and do what k_put's record form does with it; the blocks after them take a
-// put tile record (seg_xs, buffer side unused): each lane loads ONE element from the sending
-// field, negates it in registers as unpack_x_tile negates, and stores it to the receiving field
-// — 2 bytes of traffic per message byte against k_self_cs's 3. The record's axes are sorted by
-// ascending |stride| of the RECEIVING field, so a wave's stores cover whole destination runs (the
-// side that may cross xGMI), and its loads fall on a few row pieces of the sending field. Plain
-// global stores only: the epochs' system-scope release at close covers nothing else. No LDS, no
-// barrier; the planner refuses source boxes that reach into the sender's halo.
-template<int E>
-__device__ __forceinline__ void put_x_tile(const seg_xs& r, const char* __restrict__ src,
-                                           char* __restrict__ field, bool aligned)
-{
-    using V = typename vec_t<(1 << E)>::type;
-    const seg_x& s = r.x;
-    const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
-    for (uint32_t i = threadIdx.x; i < total; i += kBlock)
-    {
-        const uint32_t q0 = fastdiv(i, s.mag[0]);
-        const uint32_t c0 = i - q0 * s.tdim[0];
-        const uint32_t q1 = fastdiv(q0, s.mag[1]);
-        const uint32_t c1 = q0 - q1 * s.tdim[1];
-        const uint32_t c3 = fastdiv(q1, s.mag[2]);
-        const uint32_t c2 = q1 - c3 * s.tdim[2];
-        if (c0 >= s.act[0] || c1 >= s.act[1] || c2 >= s.act[2] || c3 >= s.act[3]) continue;
-        const char* from = src + r.src_off + int64_t(c0) * r.src_stride[0] +
-                           int64_t(c1) * r.src_stride[1] + int64_t(c2) * r.src_stride[2] +
-                           int64_t(c3) * r.src_stride[3];
-        V v;
-        if (aligned) v = vload<V>(from);
-        else
-        {
-            // a field whose base or strides are not multiples of the element size
-            unsigned char b[1 << E];
-#pragma unroll
-            for (int k = 0; k < (1 << E); ++k) b[k] = vload<unsigned char>(from + k);
-            __builtin_memcpy(&v, b, sizeof(V));
-        }
-        if (s.neg_mask)
-        {
-            uint32_t comp = s.comp0;
-            if (s.comp_pos < 4) comp += s.comp_pos == 0 ? c0 : s.comp_pos == 1 ? c1 : s.comp_pos == 2 ? c2 : c3;
-            if (comp < 2 && ((s.neg_mask >> comp) & 1u))
-            {
-                if constexpr (E == 2)
-                    v = s.neg_kind == 1 ? (v ^ 0x80000000u) : (0u - v);
-                else if constexpr (E == 3)
-                {
-                    if (s.neg_kind == 1) v.y ^= 0x80000000u;
-                    else
-                    {
-                        const uint64_t w = 0ull - ((uint64_t(v.y) << 32) | v.x);
-                        v.x = uint32_t(w);
-                        v.y = uint32_t(w >> 32);
-                    }
-                }
-            }
-        }
-        char* dst = field + s.field_off + int64_t(c0) * s.stride[0] + int64_t(c1) * s.stride[1] +
-                    int64_t(c2) * s.stride[2] + int64_t(c3) * s.stride[3];
-        if (aligned) vstore<V>(dst, v);
-        else
-        {
-            unsigned char b[1 << E];
-            __builtin_memcpy(b, &v, sizeof(V));
-#pragma unroll
-            for (int k = 0; k < (1 << E); ++k) vstore<unsigned char>(dst + k, b[k]);
-        }
-    }
-}
-
+// Cubed-sphere put: k_self_cs's walk without the buffer, the destination being any mapped field
+// (this device's or a node-local peer's through IPC). Blocks [0, n_pair_tiles) take a pair record
+// as k_put's record form does; the blocks after them take a put tile record (seg_xs, buffer side
+// unused): sending field -> receiving field — 2 bytes of traffic per message byte against
+// k_self_cs's 3.
 __global__ __launch_bounds__(kBlock) void k_put_cs(kargs_pcs a)
 {
     const seg_s* __restrict__ pairs = static_cast<const seg_s*>(a.pair_recs);
@@ -1252,49 +1098,13 @@ __global__ __launch_bounds__(kBlock) void k_put_cs(kargs_pcs a)
         {
             const seg_s s = pairs[2 * t];
             const seg_s q = pairs[2 * t + 1];
-            const uint32_t start = s.first_tile * s.tile_bytes;
-            const uint32_t end = min(start + s.tile_bytes, s.bytes);
-            const char* src = reinterpret_cast<const char*>(a.src_ptr[s.field_slot]);
-            char* dst = reinterpret_cast<char*>(a.dst_ptr[q.field_slot]);
-            int w = min(int(s.wlog2), int(q.wlog2));
-            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(src)));
-            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(dst)));
-            if (s.amode == 1 && q.amode == 1 && w >= 3)
-            {
-                if (w == 4) copy_direct<16, 1>(s, q, src, dst, start, end);
-                else copy_direct<8, 1>(s, q, src, dst, start, end);
-                continue;
-            }
-            switch (w)
-            {
-                case 4: copy_direct<16>(s, q, src, dst, start, end); break;
-                case 3: copy_direct<8>(s, q, src, dst, start, end); break;
-                case 2: copy_direct<4>(s, q, src, dst, start, end); break;
-                case 1: copy_direct<2>(s, q, src, dst, start, end); break;
-                default: copy_direct<1>(s, q, src, dst, start, end); break;
-            }
+            put_pair_tile(s, q, s.first_tile, reinterpret_cast<const char*>(a.src_ptr[s.field_slot]),
+                          reinterpret_cast<char*>(a.dst_ptr[q.field_slot]));
             continue;
         }
         const seg_xs r = xrecs[t - a.n_pair_tiles];
-        const char* src = reinterpret_cast<const char*>(a.src_ptr[r.src_slot]);
-        char* field = reinterpret_cast<char*>(a.dst_ptr[r.x.field_slot]);
-        // element-wide accesses when the source, the destination and every stride are
-        // element-aligned (uniform per tile; a mapped peer pointer's alignment is a run-time fact)
-        const uint64_t em = (1u << r.x.elog2) - 1u;
-        const bool aligned =
-            ((reinterpret_cast<uint64_t>(src) + uint64_t(r.src_off)) & em) == 0 &&
-            ((reinterpret_cast<uint64_t>(field) + uint64_t(r.x.field_off)) & em) == 0 &&
-            ((uint64_t(r.x.stride[0]) | uint64_t(r.x.stride[1]) | uint64_t(r.x.stride[2]) |
-              uint64_t(r.x.stride[3]) | uint64_t(r.src_stride[0]) | uint64_t(r.src_stride[1]) |
-              uint64_t(r.src_stride[2]) | uint64_t(r.src_stride[3])) & em) == 0;
-        switch (r.x.elog2)
-        {
-            case 4: put_x_tile<4>(r, src, field, aligned); break;
-            case 3: put_x_tile<3>(r, src, field, aligned); break;
-            case 2: put_x_tile<2>(r, src, field, aligned); break;
-            case 1: put_x_tile<1>(r, src, field, aligned); break;
-            default: put_x_tile<0>(r, src, field, aligned); break;
-        }
+        walk_x<true, false>(r.x, &r, reinterpret_cast<const char*>(a.src_ptr[r.src_slot]), nullptr,
+                            reinterpret_cast<char*>(a.dst_ptr[r.x.field_slot]));
     }
 }
 

@@ -300,9 +300,10 @@ slot_partition partition_slots(const std::vector<int32_t>& gf, const std::vector
     return p;
 }
 
-// Fill a launch's pointer slots from the caller's arrays through a group's maps.
-void fill_slots(uint64_t (&dst)[GHX_MAX_SLOTS], void* const* src, const std::vector<int32_t>& map,
-                int n_identity, const char* what)
+// Fill a launch's pointer slots from the caller's arrays through a group's maps (empty: the
+// first n_identity pointers as they are); `what` names the pointers in the null refusal.
+void fill_slots(uint64_t* dst, void* const* src, const std::vector<int32_t>& map, int n_identity,
+                const char* what)
 {
     const int n = map.empty() ? n_identity : int(map.size());
     for (int i = 0; i < n; ++i)
@@ -336,12 +337,9 @@ void upload_segments(device_tables& dt, const std::vector<seg_s>& segs)
         throw hip_error("hipMemcpy(segments)");
 }
 
-void upload_pair_records(device_tables& dt, const std::vector<seg_s>& primary,
-                         const std::vector<seg_s>& companion, const std::vector<uint32_t>& tiles)
+std::vector<seg_s> pair_records(const std::vector<seg_s>& primary, const std::vector<seg_s>& companion,
+                                const std::vector<uint32_t>& tiles)
 {
-    dt.release();
-    if (!g_tune.tile_records || tiles.empty() || !have_device()) return;
-    if (primary.size() != companion.size()) throw invalid("pair records: segment counts differ");
     std::vector<seg_s> rec(tiles.size());  // 2 per tile
     for (size_t t = 0; t < tiles.size() / 2; ++t)
     {
@@ -350,6 +348,16 @@ void upload_pair_records(device_tables& dt, const std::vector<seg_s>& primary,
         rec[2 * t].first_tile = tiles[2 * t + 1];
         rec[2 * t + 1] = companion[si];
     }
+    return rec;
+}
+
+void upload_pair_records(device_tables& dt, const std::vector<seg_s>& primary,
+                         const std::vector<seg_s>& companion, const std::vector<uint32_t>& tiles)
+{
+    dt.release();
+    if (!g_tune.tile_records || tiles.empty() || !have_device()) return;
+    if (primary.size() != companion.size()) throw invalid("pair records: segment counts differ");
+    const std::vector<seg_s> rec = pair_records(primary, companion, tiles);
     const size_t rb = rec.size() * sizeof(seg_s);
     if (hipMalloc(&dt.recs, rb) != hipSuccess) throw hip_error("hipMalloc(pair records)");
     if (hipMemcpy(dt.recs, rec.data(), rb, hipMemcpyHostToDevice) != hipSuccess)
@@ -771,8 +779,64 @@ int xplan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* s
 }
 
 // ---------------------------------------------------------------------------------------------
-// fused cubed-sphere self exchange
+// fused cubed-sphere self exchange and cubed-sphere put
 // ---------------------------------------------------------------------------------------------
+// Pair records of segments that already carry their slots: tile sizes, cache policies and the
+// dispatch order are the ordinary plans' (build_tiles, under the caller's g_tune.tile_bytes); the
+// launch is tiled by the primary side's table alone, as k_self and k_put are.
+void cs_records::build_pairs(std::vector<seg_s> p, std::vector<seg_s> q)
+{
+    if (p.empty()) return;
+    const std::vector<uint32_t> tiles = build_tiles(p, 0);
+    (void)build_tiles(q, 1);
+    pair_recs = pair_records(p, q, tiles);
+}
+
+// The tile records of the spaces that do not pair: make_tile_records of the receiving side, each
+// with the sending side of the same cells. `buffered`: the records keep the box's buffer slot
+// (a put has no buffer: slot 0).
+void cs_records::build_tiles_x(const std::vector<xsbox>& boxes, bool buffered)
+{
+    for (const xsbox& b : boxes)
+    {
+        std::vector<seg_x> recs;
+        std::vector<xtile_pos> where;
+        make_tile_records(recs, b.dst, uint16_t(b.dst.field_slot),
+                          uint16_t(buffered ? b.dst.buf_slot : 0), &where);
+        for (size_t t = 0; t < recs.size(); ++t)
+        {
+            seg_xs r{};
+            r.x = recs[t];
+            r.src_off = b.src_off;
+            for (int k = 0; k < 4; ++k) r.src_off += int64_t(where[t].origin[k]) * b.src_stride[k];
+            for (int j = 0; j < 4; ++j) r.src_stride[j] = b.src_stride[where[t].axis[j]];
+            r.src_slot = uint16_t(b.src_slot);
+            x_recs.push_back(r);
+        }
+        ++n_x_records;
+    }
+}
+
+// both tables to device memory (dev.segs: pair_recs, dev.recs: x_recs; a no-op without a device)
+void cs_records::upload(const char* what)
+{
+    if (!have_device()) return;
+    auto up = [&](void*& to, const void* from, size_t nb, const char* table) {
+        if (nb == 0) return;
+        const std::string name = std::string("(") + what + " " + table + " records)";
+        if (hipMalloc(&to, nb) != hipSuccess) throw hip_error("hipMalloc" + name);
+        if (hipMemcpy(to, from, nb, hipMemcpyHostToDevice) != hipSuccess) throw hip_error("hipMemcpy" + name);
+    };
+    up(dev.segs, pair_recs.data(), pair_recs.size() * sizeof(seg_s), "pair");
+    up(dev.recs, x_recs.data(), x_recs.size() * sizeof(seg_xs), "tile");
+}
+
+void cs_records::check_tables() const
+{
+    if ((!pair_recs.empty() && !dev.segs) || (!x_recs.empty() && !dev.recs))
+        throw hip_error("plan has no device tables (no HIP device at creation)");
+}
+
 cs_self_plan::cs_self_plan(const std::vector<seg_s>& pack, const std::vector<seg_s>& unpack,
                            const std::vector<int32_t>& gf_p, const std::vector<int32_t>& gf_u,
                            const std::vector<int32_t>& gb, const std::vector<xsbox>& boxes)
@@ -787,68 +851,27 @@ cs_self_plan::cs_self_plan(const std::vector<seg_s>& pack, const std::vector<seg
         if (max_field_slot + 1 + max_buf_slot + 1 > kCsSelfPtrs)
             throw invalid("more field and buffer slots than the fused launch's arguments hold");
     };
-    if (!pack.empty())
+    std::vector<seg_s> p = pack, q = unpack;
+    for (size_t k = 0; k < pack.size(); ++k)
     {
-        std::vector<seg_s> p = pack, q = unpack;
-        for (size_t k = 0; k < pack.size(); ++k)
-        {
-            slot(gf_p[k], gb[k]);
-            slot(gf_u[k], gb[k]);
-            p[k].field_slot = uint16_t(gf_p[k]);
-            q[k].field_slot = uint16_t(gf_u[k]);
-            p[k].buf_slot = q[k].buf_slot = uint16_t(gb[k]);
-        }
-        // tile sizes, cache policies and the dispatch order are the ordinary plans' (build_tiles),
-        // with the fused self exchange's tile size as ghx_exchange_self uses it; the launch is
-        // tiled by the pack side's table alone, as k_self is
-        const uint32_t saved = g_tune.tile_bytes;
-        g_tune.tile_bytes = g_tune.self_tile_bytes;
-        const std::vector<uint32_t> tiles = build_tiles(p, 0);
-        (void)build_tiles(q, 1);
-        g_tune.tile_bytes = saved;
-        pair_recs.resize(tiles.size());  // 2 per tile
-        for (size_t t = 0; t < tiles.size() / 2; ++t)
-        {
-            const uint32_t si = tiles[2 * t];
-            pair_recs[2 * t] = p[si];
-            pair_recs[2 * t].first_tile = tiles[2 * t + 1];
-            pair_recs[2 * t + 1] = q[si];
-        }
+        slot(gf_p[k], gb[k]);
+        slot(gf_u[k], gb[k]);
+        p[k].field_slot = uint16_t(gf_p[k]);
+        q[k].field_slot = uint16_t(gf_u[k]);
+        p[k].buf_slot = q[k].buf_slot = uint16_t(gb[k]);
     }
     for (const xsbox& b : boxes)
     {
         slot(b.dst.field_slot, b.dst.buf_slot);
         slot(b.src_slot, b.dst.buf_slot);
-        std::vector<seg_x> recs;
-        std::vector<xtile_pos> where;
-        make_tile_records(recs, b.dst, uint16_t(b.dst.field_slot), uint16_t(b.dst.buf_slot), &where);
-        for (size_t t = 0; t < recs.size(); ++t)
-        {
-            seg_xs r{};
-            r.x = recs[t];
-            r.src_off = b.src_off;
-            for (int k = 0; k < 4; ++k) r.src_off += int64_t(where[t].origin[k]) * b.src_stride[k];
-            for (int j = 0; j < 4; ++j) r.src_stride[j] = b.src_stride[where[t].axis[j]];
-            r.src_slot = uint16_t(b.src_slot);
-            x_recs.push_back(r);
-        }
-        ++n_x_records;
     }
-    if (!have_device()) return;
-    if (!pair_recs.empty())
-    {
-        const size_t nb = pair_recs.size() * sizeof(seg_s);
-        if (hipMalloc(&dev.segs, nb) != hipSuccess) throw hip_error("hipMalloc(self pair records)");
-        if (hipMemcpy(dev.segs, pair_recs.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
-            throw hip_error("hipMemcpy(self pair records)");
-    }
-    if (!x_recs.empty())
-    {
-        const size_t nb = x_recs.size() * sizeof(seg_xs);
-        if (hipMalloc(&dev.recs, nb) != hipSuccess) throw hip_error("hipMalloc(self tile records)");
-        if (hipMemcpy(dev.recs, x_recs.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
-            throw hip_error("hipMemcpy(self tile records)");
-    }
+    // the fused self exchange's tile size, as ghx_exchange_self uses it
+    const uint32_t saved = g_tune.tile_bytes;
+    g_tune.tile_bytes = g_tune.self_tile_bytes;
+    build_pairs(std::move(p), std::move(q));
+    g_tune.tile_bytes = saved;
+    build_tiles_x(boxes, true);
+    upload("self");
 }
 
 int cs_self_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
@@ -856,30 +879,18 @@ int cs_self_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, 
     const uint32_t nt = n_pair_tiles() + n_x_tiles();
     if (nt == 0) return GHX_OK;
     if (nf <= max_field_slot || nb <= max_buf_slot) throw invalid("pointer arrays do not cover the plan's slots");
-    if ((!pair_recs.empty() && !dev.segs) || (!x_recs.empty() && !dev.recs))
-        throw hip_error("plan has no device tables (no HIP device at creation)");
+    check_tables();
     kargs_cs a{};
     a.pair_recs = dev.segs;
     a.x_recs = dev.recs;
     a.n_pair_tiles = n_pair_tiles();
     a.n_x_tiles = n_x_tiles();
     a.buf_base = uint32_t(max_field_slot + 1);
-    for (int i = 0; i <= max_field_slot; ++i)
-    {
-        if (!fptr[i]) throw invalid("null field pointer");
-        a.ptr[i] = reinterpret_cast<uint64_t>(fptr[i]);
-    }
-    for (int i = 0; i <= max_buf_slot; ++i)
-    {
-        if (!bptr[i]) throw invalid("null buffer pointer");
-        a.ptr[a.buf_base + uint32_t(i)] = reinterpret_cast<uint64_t>(bptr[i]);
-    }
+    fill_slots(a.ptr, fptr, {}, max_field_slot + 1, "field");
+    fill_slots(a.ptr + a.buf_base, bptr, {}, max_buf_slot + 1, "buffer");
     return launch_self_cs(a, stream, grid_for_tiles(nt));
 }
 
-// ---------------------------------------------------------------------------------------------
-// cubed-sphere put
-// ---------------------------------------------------------------------------------------------
 cs_put_plan::cs_put_plan(const std::vector<seg_s>& from, const std::vector<seg_s>& to,
                          const std::vector<int32_t>& gs, const std::vector<int32_t>& gd,
                          const std::vector<xsbox>& boxes, uint64_t nbytes)
@@ -894,61 +905,18 @@ cs_put_plan::cs_put_plan(const std::vector<seg_s>& from, const std::vector<seg_s
         max_src_slot = std::max(max_src_slot, s);
         max_dst_slot = std::max(max_dst_slot, d);
     };
-    if (!from.empty())
+    std::vector<seg_s> p = from, q = to;
+    for (size_t k = 0; k < from.size(); ++k)
     {
-        std::vector<seg_s> p = from, q = to;
-        for (size_t k = 0; k < from.size(); ++k)
-        {
-            slot(gs[k], gd[k]);
-            p[k].field_slot = uint16_t(gs[k]);
-            q[k].field_slot = uint16_t(gd[k]);
-        }
-        // tiled by the source side's table alone, with the pack plans' tile sizes and dispatch
-        // order, as ghx_put_create's plans are
-        const std::vector<uint32_t> tiles = build_tiles(p, 0);
-        (void)build_tiles(q, 1);
-        pair_recs.resize(tiles.size());  // 2 per tile
-        for (size_t t = 0; t < tiles.size() / 2; ++t)
-        {
-            const uint32_t si = tiles[2 * t];
-            pair_recs[2 * t] = p[si];
-            pair_recs[2 * t].first_tile = tiles[2 * t + 1];
-            pair_recs[2 * t + 1] = q[si];
-        }
+        slot(gs[k], gd[k]);
+        p[k].field_slot = uint16_t(gs[k]);
+        q[k].field_slot = uint16_t(gd[k]);
     }
-    for (const xsbox& b : boxes)
-    {
-        slot(b.src_slot, b.dst.field_slot);
-        std::vector<seg_x> recs;
-        std::vector<xtile_pos> where;
-        make_tile_records(recs, b.dst, uint16_t(b.dst.field_slot), 0, &where);
-        for (size_t t = 0; t < recs.size(); ++t)
-        {
-            seg_xs r{};
-            r.x = recs[t];
-            r.src_off = b.src_off;
-            for (int k = 0; k < 4; ++k) r.src_off += int64_t(where[t].origin[k]) * b.src_stride[k];
-            for (int j = 0; j < 4; ++j) r.src_stride[j] = b.src_stride[where[t].axis[j]];
-            r.src_slot = uint16_t(b.src_slot);
-            x_recs.push_back(r);
-        }
-        ++n_x_records;
-    }
-    if (!have_device()) return;
-    if (!pair_recs.empty())
-    {
-        const size_t nb = pair_recs.size() * sizeof(seg_s);
-        if (hipMalloc(&dev.segs, nb) != hipSuccess) throw hip_error("hipMalloc(put pair records)");
-        if (hipMemcpy(dev.segs, pair_recs.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
-            throw hip_error("hipMemcpy(put pair records)");
-    }
-    if (!x_recs.empty())
-    {
-        const size_t nb = x_recs.size() * sizeof(seg_xs);
-        if (hipMalloc(&dev.recs, nb) != hipSuccess) throw hip_error("hipMalloc(put tile records)");
-        if (hipMemcpy(dev.recs, x_recs.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
-            throw hip_error("hipMemcpy(put tile records)");
-    }
+    for (const xsbox& b : boxes) slot(b.src_slot, b.dst.field_slot);
+    // the pack plans' tile sizes, as ghx_put_create's plans have
+    build_pairs(std::move(p), std::move(q));
+    build_tiles_x(boxes, false);
+    upload("put");
 }
 
 int cs_put_plan::execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const
@@ -956,24 +924,15 @@ int cs_put_plan::execute(void* const* src, int ns, void* const* dst, int nd, voi
     const uint32_t nt = n_pair_tiles() + n_x_tiles();
     if (nt == 0) return GHX_OK;
     if (ns <= max_src_slot || nd <= max_dst_slot) throw invalid("pointer arrays do not cover the plan's slots");
-    if ((!pair_recs.empty() && !dev.segs) || (!x_recs.empty() && !dev.recs))
-        throw hip_error("plan has no device tables (no HIP device at creation)");
+    check_tables();
     if (x_recs.empty())
     {
         // nothing to transform: k_put's record form over the pair records
         kargs k{};
         k.tile_recs = dev.segs;
         k.n_tiles = n_pair_tiles();
-        for (int i = 0; i <= max_src_slot; ++i)
-        {
-            if (!src[i]) throw invalid("null source field pointer");
-            k.field_ptr[i] = reinterpret_cast<uint64_t>(src[i]);
-        }
-        for (int i = 0; i <= max_dst_slot; ++i)
-        {
-            if (!dst[i]) throw invalid("null target field pointer");
-            k.buf_ptr[i] = reinterpret_cast<uint64_t>(dst[i]);
-        }
+        fill_slots(k.field_ptr, src, {}, max_src_slot + 1, "source field");
+        fill_slots(k.buf_ptr, dst, {}, max_dst_slot + 1, "target field");
         return launch_put(k, stream, grid_for_tiles(k.n_tiles));
     }
     kargs_pcs a{};
@@ -981,16 +940,8 @@ int cs_put_plan::execute(void* const* src, int ns, void* const* dst, int nd, voi
     a.x_recs = dev.recs;
     a.n_pair_tiles = n_pair_tiles();
     a.n_x_tiles = n_x_tiles();
-    for (int i = 0; i <= max_src_slot; ++i)
-    {
-        if (!src[i]) throw invalid("null source field pointer");
-        a.src_ptr[i] = reinterpret_cast<uint64_t>(src[i]);
-    }
-    for (int i = 0; i <= max_dst_slot; ++i)
-    {
-        if (!dst[i]) throw invalid("null target field pointer");
-        a.dst_ptr[i] = reinterpret_cast<uint64_t>(dst[i]);
-    }
+    fill_slots(a.src_ptr, src, {}, max_src_slot + 1, "source field");
+    fill_slots(a.dst_ptr, dst, {}, max_dst_slot + 1, "target field");
     return launch_put_cs(a, stream, grid_for_tiles(nt));
 }
 

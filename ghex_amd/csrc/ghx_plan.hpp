@@ -38,7 +38,9 @@ void upload_segments(device_tables& dt, const std::vector<seg_s>& segs);
 // Pair records of a fused launch (k_self, k_put; g_tune.tile_records): per tile of the primary
 // plan, in its dispatch order, the primary segment (with the tile's index in first_tile) and
 // the companion segment of the same index, side by side (dt.recs; a no-op without a device or
-// with tile_records off)
+// with tile_records off); pair_records builds the table on the host
+std::vector<seg_s> pair_records(const std::vector<seg_s>& primary, const std::vector<seg_s>& companion,
+                                const std::vector<uint32_t>& tiles);
 void upload_pair_records(device_tables& dt, const std::vector<seg_s>& primary,
                          const std::vector<seg_s>& companion, const std::vector<uint32_t>& tiles);
 uint64_t add_box_segments(std::vector<seg_s>& out, const ghx_field_desc& f, const ghx_box& box,
@@ -134,16 +136,26 @@ struct xsbox
     int64_t src_stride[4];  // and its byte stride per buffer axis
     int32_t src_slot;
 };
-struct cs_self_plan
+// the two record tables of a cubed-sphere launch (k_self_cs, k_put_cs) and how they are built
+struct cs_records
 {
-    std::vector<seg_s> pair_recs;  // two per pair tile: the pack segment (first_tile = the tile's
-                                   // index in it), then the unpack segment
-    std::vector<seg_xs> x_recs;    // one per self tile
+    std::vector<seg_s> pair_recs;  // two per pair tile: the pack / source segment (first_tile =
+                                   // the tile's index in it), then the unpack / target segment
+    std::vector<seg_xs> x_recs;    // one per self / put tile
     int32_t n_x_records = 0;       // spaces (boxes) behind x_recs
-    int max_field_slot = -1, max_buf_slot = -1;
     device_tables dev;             // dev.segs: pair_recs, dev.recs: x_recs
     uint32_t n_pair_tiles() const { return uint32_t(pair_recs.size() / 2); }
     uint32_t n_x_tiles() const { return uint32_t(x_recs.size()); }
+
+protected:
+    void build_pairs(std::vector<seg_s> primary, std::vector<seg_s> companion);  // slots set
+    void build_tiles_x(const std::vector<xsbox>& boxes, bool buffered);
+    void upload(const char* what);
+    void check_tables() const;  // throws when a launch would lack its device tables
+};
+struct cs_self_plan : cs_records
+{
+    int max_field_slot = -1, max_buf_slot = -1;
     // pack / unpack segments of the paired spaces (segment k of each over the same bytes, caller
     // slots gf_p / gf_u / gb) and the boxes of the others
     cs_self_plan(const std::vector<seg_s>& pack, const std::vector<seg_s>& unpack,
@@ -160,17 +172,10 @@ struct cs_self_plan
 // IPC-mapped memory. Field slots: the sender's (pair primary, seg_xs::src_slot) index the
 // source pointer array, the receiver's (pair companion, x.field_slot) the target pointer array;
 // fewer than GHX_MAX_SLOTS of each (one launch). Built without a device like cs_self_plan.
-struct cs_put_plan
+struct cs_put_plan : cs_records
 {
-    std::vector<seg_s> pair_recs;  // two per pair tile: source segment (first_tile = the tile's
-                                   // index in it), then target segment
-    std::vector<seg_xs> x_recs;    // one per put tile
-    int32_t n_x_records = 0;       // spaces (boxes) behind x_recs
     uint64_t bytes = 0;            // message bytes moved per execution
     int max_src_slot = -1, max_dst_slot = -1;
-    device_tables dev;             // dev.segs: pair_recs, dev.recs: x_recs
-    uint32_t n_pair_tiles() const { return uint32_t(pair_recs.size() / 2); }
-    uint32_t n_x_tiles() const { return uint32_t(x_recs.size()); }
     // source / target segments of the paired spaces (segment k of each over the same message
     // bytes; gs / gd: the source / target field slot of each) and the boxes of the others
     // (dst.field_slot: the target slot, src_slot: the source slot)

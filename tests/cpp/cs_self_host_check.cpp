@@ -1,217 +1,39 @@
 // cs_self_host_check — stand-alone host program (its own main; links the library's sources) for
 // the fused cubed-sphere self exchange. It plans the cubed-sphere fixture geometries with all
 // domains on one rank (ghx_cs_pattern_create, ghx_cs_exchange_create, no device), then replays
-// every pair record and every self tile record (seg_xs) of the fused plan on the host, exactly as
-// k_self_cs indexes them, with every source, buffer and destination access bounds-checked. The
-// send buffers and the fields it leaves are compared, whole, with the reference's semantics:
+// every pair record and every self tile record (seg_xs) of the fused plan on the host, with the
+// kernels' own address arithmetic (ghx_addr.hpp) exactly as k_self_cs indexes them, with every
+// source, buffer and destination access bounds-checked. The send buffers and the fields it leaves
+// are compared, whole, with the reference's semantics:
 // pack = the sender's dense box in its layout order (regular/field_descriptor.hpp:114-150),
 // unpack = the rotating, negating read of cubed_sphere/field_descriptor.hpp:81-108. It also
 // checks that every payload byte of every buffer and every halo byte is written exactly once and
 // that no byte the launch reads is a byte it writes. Elements of 1 to 16 bytes, both negations
 // at 4 and 8 bytes, two fields of different width in one exchange, each at the default tile size
 // and at x_tile_elems 32, 48 and 4096. Built with -fsanitize=address,undefined by
-// tools/cs_self_host_sanitize.sh; needs no GPU.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <vector>
+// tools/cs_host_sanitize.sh; needs no GPU.
+#include "cs_check.hpp"
 
-#include "../../ghex_amd/csrc/ghx_cubed_sphere.hpp"
-#include "../../ghex_amd/csrc/ghx_exchange.hpp"
-
-using namespace ghx;
+using namespace cs_check;
 
 namespace
 {
-int g_fail = 0;
-#define CHECK(c)                                                                 \
-    do                                                                           \
-    {                                                                            \
-        if (!(c))                                                                \
-        {                                                                        \
-            std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c);              \
-            if (++g_fail > 20) std::exit(1);                                     \
-        }                                                                        \
-    } while (0)
-
-struct config
-{
-    int c, levels, halos[4], nx, ny;  // nx x ny domains per tile
-};
-
-struct spec
-{
-    int elem, nc, vector, kind;
-};
-
-uint32_t fdiv(uint32_t n, magic_u32 m)
-{
-    const uint32_t t = uint32_t((uint64_t(m.m) * n) >> 32);
-    return (t + ((n - t) >> m.s1)) >> m.s2;
-}
-
-struct field
-{
-    ghx_field_desc d;
-    ghx_cs_item cs;
-    int dom;
-    spec sp;
-    std::vector<unsigned char> mem, want;
-    std::vector<unsigned char> written, read;  // per byte
-};
-
-// a (x, y, z, k) field of one domain with `h` halo cells, memory order by `layout`
-field make_field(const ghx_cs_domain& dom, int c, int levels, int h, const int* layout, const spec& s)
-{
-    field f{};
-    const int shape[4] = {dom.x_last - dom.x_first + 1 + 2 * h, dom.y_last - dom.y_first + 1 + 2 * h,
-                          levels, s.nc};
-    f.d.dim = 4;
-    f.d.elem_size = s.elem;
-    int64_t stride = s.elem;
-    for (int v = 3; v >= 0; --v)
-        for (int d = 0; d < 4; ++d)
-            if (layout[d] == v)
-            {
-                f.d.byte_strides[d] = stride;
-                stride *= shape[d];
-            }
-    for (int d = 0; d < 4; ++d)
-    {
-        f.d.layout[d] = layout[d];
-        f.d.offsets[d] = d < 2 ? h : 0;
-        f.d.extents[d] = shape[d];
-    }
-    f.d.num_components = s.nc;
-    f.d.has_components = 1;
-    f.cs = {dom.tile, dom.x_first, dom.y_first, c, s.vector, s.kind};
-    f.sp = s;
-    f.mem.resize(size_t(stride));
-    f.written.assign(size_t(stride), 0);
-    f.read.assign(size_t(stride), 0);
-    return f;
-}
-
-// an element of up to 16 bytes, little endian: its first `elem` bytes count
-struct value
-{
-    uint64_t lo = 0, hi = 0;
-};
-
-value truncated(value v, int elem)
-{
-    if (elem < 16) v.hi = 0;
-    if (elem < 8) v.lo &= (uint64_t(1) << (8 * elem)) - 1;
-    return v;
-}
-
-// sign-bit flip (kind 1) or two's-complement negation (kind 2) of an element of any width
-value negated(value v, int elem, int kind)
-{
-    if (kind == 1)
-    {
-        if (elem == 16) v.hi ^= uint64_t(1) << 63;
-        else v.lo ^= uint64_t(1) << (8 * elem - 1);
-        return v;
-    }
-    value r;
-    r.lo = uint64_t(0) - v.lo;
-    r.hi = ~v.hi + (v.lo == 0 ? 1 : 0);
-    return truncated(r, elem);
-}
-
-// field_offset_s of ghx_kernels.hip
-int64_t offset_s(const seg_s& s, uint32_t p)
-{
-    const uint32_t row = fdiv(p, s.mag_row);
-    const uint32_t col = p - row * s.row_bytes;
-    const uint32_t q0 = fdiv(row, s.mag_ext[0]);
-    const uint32_t c0 = row - q0 * s.ext[0];
-    const uint32_t q1 = fdiv(q0, s.mag_ext[1]);
-    const uint32_t c1 = q0 - q1 * s.ext[1];
-    const uint32_t q2 = fdiv(q1, s.mag_ext[2]);
-    const uint32_t c2 = q1 - q2 * s.ext[2];
-    return s.field_off + int64_t(c0) * s.stride[0] + int64_t(c1) * s.stride[1] +
-           int64_t(c2) * s.stride[2] + int64_t(q2) * s.stride[3] + int64_t(col);
-}
-
-// field_offset_f<NDIV> of ghx_kernels.hip, relative to field_off; every product's operands must
-// be below 2^24 (v_mul_u32_u24)
-uint32_t mul24(uint32_t a, uint32_t b)
-{
-    CHECK(a < (1u << 24) && b < (1u << 24));
-    return a * b;
-}
-
-int64_t offset_f(const seg_s& s, uint32_t p)
-{
-    const uint32_t row = fdiv(p, s.mag_row);
-    uint32_t off = p - mul24(row, s.row_bytes);
-    const uint32_t q0 = fdiv(row, s.mag_ext[0]);
-    off += mul24(row - mul24(q0, s.ext[0]), uint32_t(s.stride[0]));
-    if (s.amode == 1) off += mul24(q0, uint32_t(s.stride[1]));
-    else
-    {
-        const uint32_t q1 = fdiv(q0, s.mag_ext[1]);
-        off += mul24(q0 - mul24(q1, s.ext[1]), uint32_t(s.stride[1]));
-        off += mul24(q1, uint32_t(s.stride[2]));
-    }
-    return s.field_off + int64_t(off);
-}
-
 void run(const config& cfg, const int* layout, const std::vector<spec>& specs, int x_tile_elems)
 {
-    // a planning knob: read when the exchange is created
-    if (x_tile_elems) CHECK(ghx_tune("x_tile_elems", x_tile_elems) == GHX_OK);
-    std::vector<ghx_cs_domain> doms;
-    const int sx = cfg.c / cfg.nx, sy = cfg.c / cfg.ny;
-    for (int t = 0; t < 6; ++t)
-        for (int j = 0; j < cfg.ny; ++j)
-            for (int i = 0; i < cfg.nx; ++i)
-                doms.push_back({0, t, i * sx, (i + 1) * sx - 1, j * sy, (j + 1) * sy - 1});
-    ghx_pattern* pat = nullptr;
-    CHECK(ghx_cs_pattern_create(cfg.c, cfg.levels, doms.data(), int(doms.size()), cfg.halos, 0,
-                                &pat) == GHX_OK);
-    if (!pat) return;
-    int h = 1;
-    for (int k = 0; k < 4; ++k) h = std::max(h, cfg.halos[k]);
-    // items: field set by field set, each over all domains
-    std::vector<field> fields;
+    fixture fx(cfg, layout, specs);
+    if (!fx.pat) return;
+    std::vector<field>& fields = fx.fields;
     std::vector<ghx_exchange_item> items;
     std::vector<ghx_cs_item> cs;
-    for (const spec& s : specs)
-        for (size_t a = 0; a < doms.size(); ++a)
-        {
-            fields.push_back(make_field(doms[a], cfg.c, cfg.levels, h, layout, s));
-            field& f = fields.back();
-            f.dom = int(a);
-            uint64_t x = 0x9E3779B97F4A7C15ull * (fields.size() + 1);
-            for (unsigned char& b : f.mem)
-            {
-                x = x * 6364136223846793005ull + 1442695040888963407ull;
-                b = static_cast<unsigned char>(x >> 56);
-            }
-            f.want = f.mem;
-            ghx_exchange_item it{};
-            it.pattern = pat;
-            it.local_index = int32_t(a);
-            it.kind = 0;
-            it.field = f.d;
-            it.align = s.elem;
-            items.push_back(it);
-            cs.push_back(f.cs);
-        }
+    fx.items(items, cs);
+    // a planning knob: read when the exchange is created
+    if (x_tile_elems) CHECK(ghx_tune("x_tile_elems", x_tile_elems) == GHX_OK);
     ghx_exchange* ex = nullptr;
     const int rc = ghx_cs_exchange_create(items.data(), cs.data(), int(items.size()), &ex);
     if (x_tile_elems) CHECK(ghx_tune("reset", 0) == GHX_OK);
     if (rc != GHX_OK) std::printf("create: %s\n", ghx_last_error());
     CHECK(rc == GHX_OK);
-    if (!ex)
-    {
-        ghx_pattern_destroy(pat);
-        return;
-    }
+    if (!ex) return;
     int32_t fusable = 0, npair = 0, nxrec = 0, nxtiles = 0;
     CHECK(ghx_cs_self_info(ex, &fusable, &npair, &nxrec, &nxtiles) == GHX_OK);
     if (!fusable) std::printf("not fusable: %s\n", ghx_last_error());
@@ -224,7 +46,6 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, i
     if (!fusable || !ex->cs_self)
     {
         ghx_exchange_destroy(ex);
-        ghx_pattern_destroy(pat);
         return;
     }
     const cs_self_plan& sp = *ex->cs_self;
@@ -239,43 +60,12 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, i
         want.emplace_back(size_t(ex->send[b].size), static_cast<unsigned char>(0x5A));
         bwritten.emplace_back(size_t(ex->send[b].size), static_cast<unsigned char>(0));
     }
-
-    // ------------------------------------------------------------------ the replay's accessors
-    auto src_read = [&](int slot, int64_t off, unsigned char* to, size_t n) {
-        const bool ok = slot >= 0 && size_t(slot) < fields.size() && off >= 0 &&
-                        size_t(off) + n <= fields[size_t(slot)].mem.size();
-        CHECK(ok);
-        if (!ok) return false;
-        std::memcpy(to, fields[size_t(slot)].mem.data() + off, n);
-        for (size_t i = 0; i < n; ++i) fields[size_t(slot)].read[size_t(off) + i] = 1;
-        return true;
-    };
-    auto buf_write = [&](int slot, uint64_t off, const unsigned char* from, size_t n) {
+    auto buf_write = [&](int slot, uint64_t off, const void* from, size_t n) {
         const bool ok = slot >= 0 && size_t(slot) < got.size() && off + n <= got[size_t(slot)].size();
         CHECK(ok);
         if (!ok) return;
         std::memcpy(got[size_t(slot)].data() + off, from, n);
         for (size_t i = 0; i < n; ++i) ++bwritten[size_t(slot)][size_t(off) + i];
-    };
-    // the destination writes are kept aside and applied at the end: the launch's workgroups run
-    // in no order, so a read must never see a write (checked below through the read/written maps)
-    struct dwrite
-    {
-        int slot;
-        int64_t off;
-        unsigned char b[16];
-        size_t n;
-    };
-    std::vector<dwrite> dwrites;
-    auto dst_write = [&](int slot, int64_t off, const unsigned char* from, size_t n) {
-        const bool ok = slot >= 0 && size_t(slot) < fields.size() && off >= 0 &&
-                        size_t(off) + n <= fields[size_t(slot)].mem.size();
-        CHECK(ok);
-        if (!ok) return;
-        dwrite w{slot, off, {}, n};
-        std::memcpy(w.b, from, n);
-        dwrites.push_back(w);
-        for (size_t i = 0; i < n; ++i) ++fields[size_t(slot)].written[size_t(off) + i];
     };
 
     // ------------------------------------------------------------------ pair records (k_self's)
@@ -293,13 +83,13 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, i
         CHECK(s.row_bytes % (1u << s.wlog2) == 0 && q.row_bytes % (1u << q.wlog2) == 0);
         for (uint32_t p = start; p < end; ++p)
         {
-            const int64_t fo = offset_s(s, p), uo = offset_s(q, p);
+            const int64_t fo = field_offset_s(s, p), uo = field_offset_s(q, p);
             if (s.amode) CHECK(offset_f(s, p) == fo);
             if (q.amode) CHECK(offset_f(q, p) == uo);
             unsigned char v = 0;
-            if (!src_read(s.field_slot, fo, &v, 1)) continue;
+            if (!fx.src_read(s.field_slot, fo, &v, 1)) continue;
             buf_write(s.buf_slot, s.buf_off + p, &v, 1);
-            dst_write(q.field_slot, uo, &v, 1);
+            fx.dst_write(q.field_slot, uo, &v, 1);
         }
         pair_bytes += end - start;
     }
@@ -309,38 +99,18 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, i
     for (const seg_xs& r : sp.x_recs)
     {
         const seg_x& s = r.x;
-        const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
-        CHECK(total <= uint32_t(x_tile_elems ? x_tile_elems : 256));
         const size_t e = size_t(1) << s.elog2;
-        uint32_t stored = 0;
-        for (uint32_t i = 0; i < total; ++i)
-        {
-            const uint32_t q0 = fdiv(i, s.mag[0]), c0 = i - q0 * s.tdim[0];
-            const uint32_t q1 = fdiv(q0, s.mag[1]), c1 = q0 - q1 * s.tdim[1];
-            const uint32_t c3 = fdiv(q1, s.mag[2]), c2 = q1 - c3 * s.tdim[2];
-            CHECK(c3 < s.tdim[3]);
-            if (c0 >= s.act[0] || c1 >= s.act[1] || c2 >= s.act[2] || c3 >= s.act[3]) continue;
-            const uint32_t cc[4] = {c0, c1, c2, c3};
-            uint64_t bi = 0;
-            int64_t from = r.src_off, to = s.field_off;
-            for (int k = 0; k < 4; ++k)
-            {
-                bi += uint64_t(cc[k]) * s.bstride[k];
-                from += int64_t(cc[k]) * r.src_stride[k];
-                to += int64_t(cc[k]) * s.stride[k];
-            }
+        replay_tile(s, x_tile_elems, [&](const uint32_t (&c)[4], int64_t to) {
             value v;
-            if (!src_read(r.src_slot, from, reinterpret_cast<unsigned char*>(&v), e)) continue;
-            buf_write(s.buf_slot, s.buf_off + (bi << s.elog2), reinterpret_cast<unsigned char*>(&v), e);
-            const uint32_t comp = s.comp0 + (s.comp_pos < 4 ? cc[s.comp_pos] : 0);
-            if (comp < 2 && ((s.neg_mask >> comp) & 1)) v = negated(v, int(e), s.neg_kind);
-            dst_write(s.field_slot, to, reinterpret_cast<unsigned char*>(&v), e);
-            ++stored;
-        }
-        CHECK(uint64_t(stored) << s.elog2 == s.bytes);
+            if (!fx.src_read(r.src_slot, affine_offset(r.src_off, r.src_stride, c), &v, e)) return false;
+            buf_write(s.buf_slot, s.buf_off + (uint64_t(tile_cell(s, c)) << s.elog2), &v, e);
+            v = stored_value(s, c, v);
+            fx.dst_write(s.field_slot, to, &v, e);
+            return true;
+        });
         x_bytes += s.bytes;
     }
-    for (const dwrite& w : dwrites) std::memcpy(fields[size_t(w.slot)].mem.data() + w.off, w.b, w.n);
+    fx.apply();
 
     // ------------------------------------------------------------------ the reference: pack
     // communication_object::allocate's layout: per domain pair the fields in item order, each
@@ -355,10 +125,8 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, i
     uint64_t payload = 0;
     for (field& f : fields)
     {
-        const domain_pattern& dp = pat->doms[size_t(f.dom)];
+        const domain_pattern& dp = fx.pat->doms[size_t(f.dom)];
         const int elem = f.sp.elem, nc = f.sp.nc;
-        int order[4];
-        for (int d = 0; d < 4; ++d) order[3 - f.d.layout[d]] = d;  // fastest first
         for (const halo_entry& e : dp.send)
         {
             const size_t b = buffer_of(e.key.remote_id, dp.id);
@@ -367,123 +135,62 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, i
             at = (at + uint64_t(elem) - 1) / uint64_t(elem) * uint64_t(elem);
             for (const is_pair& bx : e.boxes)
             {
-                const int64_t ext[4] = {bx.ll[0] - bx.lf[0] + 1, bx.ll[1] - bx.lf[1] + 1,
-                                        bx.ll[2] - bx.lf[2] + 1, nc};
-                int64_t bstride[4], acc = elem;
-                for (int k = 0; k < 4; ++k)
-                {
-                    bstride[order[k]] = acc;
-                    acc *= ext[order[k]];
-                }
-                CHECK(at + uint64_t(acc) <= want[b].size());
-                if (at + uint64_t(acc) > want[b].size()) continue;
+                const dense_box box(f, bx.lf, bx.ll);
+                CHECK(at + uint64_t(box.bytes) <= want[b].size());
+                if (at + uint64_t(box.bytes) > want[b].size()) continue;
                 for (int x = bx.lf[0]; x <= bx.ll[0]; ++x)
                     for (int y = bx.lf[1]; y <= bx.ll[1]; ++y)
                         for (int z = bx.lf[2]; z <= bx.ll[2]; ++z)
                             for (int k = 0; k < nc; ++k)
                             {
-                                const int64_t loc = (x - bx.lf[0]) * bstride[0] + (y - bx.lf[1]) * bstride[1] +
-                                                    (z - bx.lf[2]) * bstride[2] + k * bstride[3];
-                                const int64_t off = (x + f.d.offsets[0]) * f.d.byte_strides[0] +
-                                                    (y + f.d.offsets[1]) * f.d.byte_strides[1] +
-                                                    z * f.d.byte_strides[2] + k * f.d.byte_strides[3];
-                                // `want` of the field is still its initial state here
-                                std::memcpy(want[b].data() + at + uint64_t(loc), f.want.data() + off, size_t(elem));
+                                const int64_t loc = box.at({x - bx.lf[0], y - bx.lf[1], z - bx.lf[2], k});
+                                // `first` is the field's initial state
+                                std::memcpy(want[b].data() + at + uint64_t(loc),
+                                            f.first.data() + f.offset(x, y, z, k), size_t(elem));
                             }
-                at += uint64_t(acc);
-                payload += uint64_t(acc);
+                at += uint64_t(box.bytes);
+                payload += uint64_t(box.bytes);
             }
         }
     }
     // ------------------------------------------------------------------ the reference: unpack
     fill.clear();
-    uint64_t cells = 0;
-    for (field& f : fields)
-    {
-        const ghx_cs_domain& dom = doms[size_t(f.dom)];
-        const domain_pattern& dp = pat->doms[size_t(f.dom)];
-        const int elem = f.sp.elem, nc = f.sp.nc;
-        int order[4];
-        for (int d = 0; d < 4; ++d) order[3 - f.d.layout[d]] = d;
-        for (const halo_entry& e : dp.recv)
-        {
-            const size_t b = buffer_of(dp.id, e.key.remote_id);
-            if (b >= ex->send.size()) continue;
-            uint64_t& at = fill[{dp.id, e.key.remote_id}];
-            at = (at + uint64_t(elem) - 1) / uint64_t(elem) * uint64_t(elem);
-            for (size_t i = 0; i < e.boxes.size(); ++i)
-            {
-                const is_pair& bx = e.boxes[i];
-                const int n = e.tiles[i] == dom.tile ? -1 : cs_neighbour_index(dom.tile, e.tiles[i]);
-                const int64_t ext[4] = {bx.gl[0] - bx.gf[0] + 1, bx.gl[1] - bx.gf[1] + 1,
-                                        bx.gl[2] - bx.gf[2] + 1, nc};
-                int64_t bstride[4], acc = elem;
-                for (int k = 0; k < 4; ++k)
-                {
-                    bstride[order[k]] = acc;
-                    acc *= ext[order[k]];
-                }
-                CHECK(at + uint64_t(acc) <= want[b].size());
-                if (at + uint64_t(acc) > want[b].size()) continue;
-                for (int x = bx.lf[0]; x <= bx.ll[0]; ++x)
-                    for (int y = bx.lf[1]; y <= bx.ll[1]; ++y)
-                        for (int z = bx.lf[2]; z <= bx.ll[2]; ++z)
-                            for (int k = 0; k < nc; ++k)
-                            {
-                                int32_t g[2] = {x + dom.x_first, y + dom.y_first};
-                                bool neg = false;
-                                if (n >= 0)
-                                {
-                                    const cs_transform& t = cs_transform_of(dom.tile, n);
-                                    t.apply(x + dom.x_first, y + dom.y_first, cfg.c, g);
-                                    neg = f.sp.vector && ((k == 0 && t.r[2] == -1) || (k == 1 && t.r[1] == -1));
-                                }
-                                const int64_t bc[4] = {g[0] - bx.gf[0], g[1] - bx.gf[1], z - bx.gf[2], k};
-                                int64_t loc = 0;
-                                for (int q = 0; q < 4; ++q)
-                                {
-                                    CHECK(bc[q] >= 0 && bc[q] < ext[q]);
-                                    loc += bc[q] * bstride[q];
-                                }
-                                value v;
-                                std::memcpy(&v, want[b].data() + at + uint64_t(loc), size_t(elem));
-                                if (neg) v = negated(v, elem, f.sp.kind);
-                                const int64_t off = (x + f.d.offsets[0]) * f.d.byte_strides[0] +
-                                                    (y + f.d.offsets[1]) * f.d.byte_strides[1] +
-                                                    z * f.d.byte_strides[2] + k * f.d.byte_strides[3];
-                                std::memcpy(f.want.data() + off, &v, size_t(elem));
-                                ++cells;
-                            }
-                at += uint64_t(acc);
-            }
-        }
-    }
+    size_t b = 0;      // of the space being walked: its buffer,
+    uint64_t base = 0; // its first byte there
+    const uint64_t cells = for_each_halo_cell(
+        fx,
+        [&](field& f, const halo_entry& e, size_t i) {
+            const int32_t id = fx.pat->doms[size_t(f.dom)].id;
+            b = buffer_of(id, e.key.remote_id);
+            if (b >= ex->send.size()) return false;
+            uint64_t& at = fill[{id, e.key.remote_id}];
+            const uint64_t elem = uint64_t(f.sp.elem);
+            base = at = (at + elem - 1) / elem * elem;
+            const dense_box box(f, e.boxes[i].gf, e.boxes[i].gl);
+            CHECK(base + uint64_t(box.bytes) <= want[b].size());
+            if (base + uint64_t(box.bytes) > want[b].size()) return false;
+            at += uint64_t(box.bytes);
+            return true;
+        },
+        [&](field& f, const halo_entry& e, size_t i, const halo_cell& h) {
+            const is_pair& bx = e.boxes[i];
+            const dense_box box(f, bx.gf, bx.gl);
+            const int64_t loc = box.at({h.g[0] - bx.gf[0], h.g[1] - bx.gf[1], h.z - bx.gf[2], h.k});
+            value v;
+            std::memcpy(&v, want[b].data() + base + uint64_t(loc), size_t(f.sp.elem));
+            if (h.neg) v = negated(v, f.sp.elem, f.sp.kind);
+            std::memcpy(f.want.data() + f.offset(h.x, h.y, h.z, h.k), &v, size_t(f.sp.elem));
+        });
     // ------------------------------------------------------------------ comparison
     CHECK(pair_bytes + x_bytes == payload);
-    for (size_t b = 0; b < got.size(); ++b)
+    for (size_t k = 0; k < got.size(); ++k)
     {
-        CHECK(got[b] == want[b]);
-        uint64_t once = 0, more = 0;
-        for (unsigned char w : bwritten[b])
-        {
-            once += w == 1;
-            more += w > 1;
-        }
+        CHECK(got[k] == want[k]);
+        uint64_t more = 0;
+        for (unsigned char w : bwritten[k]) more += w > 1;
         CHECK(more == 0);
-        (void)once;
     }
-    uint64_t halo_bytes = 0;
-    for (const field& f : fields)
-    {
-        CHECK(f.mem == f.want);
-        for (size_t i = 0; i < f.mem.size(); ++i)
-        {
-            CHECK(f.written[i] <= 1);
-            CHECK(!(f.written[i] && f.read[i]));  // no cell the launch reads is one it writes
-            halo_bytes += f.written[i];
-        }
-    }
-    CHECK(halo_bytes == payload);
+    CHECK(fx.check_accesses() == payload);
     std::printf("c=%d levels=%d layout=%d%d%d%d fields=%zu (elem %d..) x_tile_elems=%d: %llu halo "
                 "cells, %d rotated spaces, %d pair tiles, %d self records in %d tiles\n",
                 cfg.c, cfg.levels, layout[0], layout[1], layout[2], layout[3], specs.size(),
@@ -491,7 +198,6 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, i
                 static_cast<unsigned long long>(cells), nrot, npair, nxrec, nxtiles);
     CHECK(nxtiles >= nxrec);
     ghx_exchange_destroy(ex);
-    ghx_pattern_destroy(pat);
 }
 }  // namespace
 
