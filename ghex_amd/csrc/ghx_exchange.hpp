@@ -1,6 +1,7 @@
 // ghx_exchange.hpp — the exchange plan behind the opaque ghx_exchange handle
 // (communication_object::allocate semantics, include/ghex/communication_object.hpp:483-566,
-// 1003-1067), shared by the C ABI (ghx_abi.cpp) and the per-peer pipeline (ghx_pipeline.cpp).
+// 1003-1067) and the put plan behind ghx_put, shared by the C ABI (ghx_abi.cpp) and the per-peer
+// pipeline (ghx_pipeline.cpp); ghx_exchange.cpp plans and executes them.
 #pragma once
 
 #include <memory>
@@ -37,7 +38,7 @@ struct exchange_plan
     parity_cfg mixed_parity;  // the mixed pack launch's double-buffered send buffers (direct)
     parity_cfg dir_parity[2];  // ghx_exchange_set_parity per direction (the per-buffer plans too)
     int32_t n_items = 0;
-    mutable int self_ok = -1;  // lazily checked: may pack and unpack be fused (all self)?
+    bool self_ok = false;  // may pack and unpack be fused (all self)? Set by make_exchange.
 
     // The planner's entries per direction (0 send, 1 recv), kept for per-buffer plans; boxes
     // point into box_store, unstructured lids into the pattern (which outlives the exchange,
@@ -62,34 +63,7 @@ struct exchange_plan
     std::unique_ptr<cs_self_plan> cs_self;
     std::string cs_self_reason;
 
-    void make_split()
-    {
-        if (split) return;
-        if (cs_rotated > 0)
-            throw invalid("per-buffer plans are not available on a cubed-sphere exchange with "
-                          "rotated spaces (the per-buffer unpack does not rotate)");
-        for (int dir = 0; dir < 2; ++dir)
-        {
-            const size_t nb = dir == 0 ? send.size() : recv.size();
-            bplan[dir].clear();
-            ubplan[dir].clear();
-            bplan[dir].resize(nb);
-            ubplan[dir].resize(nb);
-            for (size_t b = 0; b < nb; ++b)
-            {
-                std::vector<ghx_pack_entry> se;
-                for (const auto& e : entries[dir])
-                    if (size_t(e.buffer_slot) == b) se.push_back(e);
-                std::vector<ghx_upack_entry> ue;
-                for (const auto& e : uentries[dir])
-                    if (size_t(e.buffer_slot) == b) ue.push_back(e);
-                if (!se.empty()) bplan[dir][b] = std::make_unique<splan>(se.data(), int(se.size()), dir);
-                if (!ue.empty()) ubplan[dir][b] = std::make_unique<uplan>(ue.data(), int(ue.size()), dir);
-            }
-        }
-        split = true;
-        for (int dir = 0; dir < 2; ++dir) set_split_parity(dir);
-    }
+    void make_split();  // the per-buffer plans (ghx_exchange_split)
 
     // the per-buffer plans use the copies ghx_exchange_set_parity selected, like the whole ones
     void set_split_parity(int dir)
@@ -102,33 +76,15 @@ struct exchange_plan
 
     // one buffer's pack (dir 0) or unpack (dir 1); the pointer arrays are the whole exchange's
     int execute_buffer(int dir, int b, void* const* fptr, int nf, void* const* bptr, int nb,
-                       void* stream) const
-    {
-        if (!split) throw invalid("exchange is not split (ghx_exchange_split)");
-        const size_t n = dir == 0 ? send.size() : recv.size();
-        if (b < 0 || size_t(b) >= n) throw invalid("buffer index out of range");
-        if (nb < int(n)) throw invalid("too few buffers");
-        int rc = GHX_OK;
-        if (bplan[dir][size_t(b)]) rc = bplan[dir][size_t(b)]->execute(fptr, nf, bptr, nb, stream);
-        if (rc == GHX_OK && ubplan[dir][size_t(b)])
-            rc = ubplan[dir][size_t(b)]->execute(fptr, nf, bptr, nb, stream);
-        return rc;
-    }
+                       void* stream) const;
 
     // Every recv buffer aliases the send buffer of the same pair, and pack segment k and unpack
     // segment k cover the same buffer bytes (the launch tiles by the pack plan's table).
-    bool self_fusable() const
-    {
-        if (self_ok >= 0) return self_ok == 1;
-        bool ok = cs_rotated == 0 && !upack && !uunpack && spack && sunpack && send.size() == recv.size() &&
-                  !spack->grouped() && !sunpack->grouped();
-        for (size_t i = 0; ok && i < send.size(); ++i)
-            ok = send[i].first_id == recv[i].first_id && send[i].second_id == recv[i].second_id &&
-                 send[i].size == recv[i].size;
-        if (ok) ok = same_messages(*spack, *sunpack);
-        self_ok = ok ? 1 : 0;
-        return ok;
-    }
+    bool self_fusable() const { return self_ok; }
+    // the fused launches: the all-self exchange (ghx_exchange_self) and the mixed pack
+    // (ghx_exchange_pack_self), k_self over the pack plan's tiles
+    int execute_self(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
+    int execute_pack_self(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 
     // Segment a of a launch's primary plan and its companion b (the unpack side of a fused self
     // tile, the target side of a put) cover the same buffer bytes with the same rows. Tiling is
@@ -146,9 +102,9 @@ struct exchange_plan
     // pack segment k and unpack segment k cover the same buffer bytes (same_message)
     static bool same_messages(const splan& p, const splan& q)
     {
-        bool ok = p.host_segs.size() == q.host_segs.size();
-        for (size_t k = 0; ok && k < p.host_segs.size(); ++k)
-            ok = same_message(p.host_segs[k], q.host_segs[k]);
+        const std::vector<seg_s>&a = p.first().host_segs, &b = q.first().host_segs;
+        bool ok = a.size() == b.size();
+        for (size_t k = 0; ok && k < a.size(); ++k) ok = same_message(a[k], b[k]);
         return ok;
     }
 };
@@ -166,26 +122,21 @@ struct ghx_exchange : ghx::exchange_plan
 struct ghx_put
 {
     std::unique_ptr<ghx::splan> from, to;
-    ghx_put(const ghx_pack_entry* src, int n_src, const ghx_pack_entry* dst, int n_dst)
-    : from(new ghx::splan(src, n_src, 0)), to(new ghx::splan(dst, n_dst, 1))
-    {
-        bool ok = from->host_segs.size() == to->host_segs.size() && from->bytes == to->bytes;
-        for (size_t k = 0; ok && k < from->host_segs.size(); ++k)
-        {
-            const auto& a = from->host_segs[k];
-            const auto& b = to->host_segs[k];
-            ok = ghx::exchange_plan::same_message(a, b) && a.n_outer == b.n_outer;
-            for (int d = 0; ok && d < 4; ++d) ok = a.ext[d] == b.ext[d];
-        }
-        if (!ok)
-            throw ghx::invalid("source and target iteration spaces do not describe the same "
-                               "message bytes (shapes, order, element sizes or row structure differ)");
-        if (from->grouped() || to->grouped())
-            throw ghx::invalid("a put plan takes at most 64 source and 64 target fields (one launch)");
-        ghx::upload_pair_records(recs, from->host_segs, to->host_segs, from->host_tiles);
-    }
     ghx::device_tables recs;  // pair records (source segment with tile index, target segment)
     // a put made by ghx_cs_put_create: `cs` alone (pair records and put tile records, k_put_cs)
     std::unique_ptr<ghx::cs_put_plan> cs;
-    explicit ghx_put(std::unique_ptr<ghx::cs_put_plan> p) : cs(std::move(p)) {}
+    ghx_put(const ghx_pack_entry* src, int n_src, const ghx_pack_entry* dst, int n_dst);
+    explicit ghx_put(std::unique_ptr<ghx::cs_put_plan> p);
+    int execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const;
 };
+
+namespace ghx
+{
+// ghx_exchange_create (cs = null) and ghx_cs_exchange_create (one cubed-sphere item per item)
+std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, const ghx_cs_item* cs,
+                                            int32_t n_items);
+// the put plan of ghx_cs_put_create; throws `invalid` with the reason for what a put cannot serve
+std::unique_ptr<cs_put_plan> build_cs_put(const ghx_pack_entry* src, int n_src,
+                                          const ghx_pack_entry* dst, int n_dst, const ghx_cs_item* cs,
+                                          const ghx_box* const* global, const int32_t* const* tiles);
+}  // namespace ghx

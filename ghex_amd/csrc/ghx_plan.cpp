@@ -300,8 +300,64 @@ slot_partition partition_slots(const std::vector<int32_t>& gf, const std::vector
     return p;
 }
 
-// Fill a launch's pointer slots from the caller's arrays through a group's maps (empty: the
-// first n_identity pointers as they are); `what` names the pointers in the null refusal.
+// The launch groups of a plan's segments (gf / gb: the caller's slots of each): the partition,
+// each group's segments with their local slots, its tile table and its device tables.
+template<typename Seg>
+std::vector<launch_group<Seg>> build_groups(const std::vector<Seg>& segs, const std::vector<int32_t>& gf,
+                                            const std::vector<int32_t>& gb, int direction)
+{
+    slot_partition part = partition_slots(gf, gb);
+    std::vector<launch_group<Seg>> groups(part.segs.size());
+    for (size_t g = 0; g < groups.size(); ++g)
+    {
+        launch_group<Seg>& grp = groups[g];
+        grp.fmap = std::move(part.fmap[g]);
+        grp.bmap = std::move(part.bmap[g]);
+        for (uint32_t k : part.segs[g])
+        {
+            Seg x = segs[k];
+            x.field_slot = uint16_t(part.lf[k]);
+            x.buf_slot = uint16_t(part.lb[k]);
+            grp.host_segs.push_back(x);
+        }
+        grp.host_tiles = build_tiles(grp.host_segs, direction);
+        grp.n_tiles = uint32_t(grp.host_tiles.size() / 2);
+        upload(grp.dev, grp.host_segs, grp.host_tiles);
+    }
+    return groups;
+}
+
+// A plan's execution: one launch per group that has tiles, in order on one stream. Per group the
+// kargs hold its device tables, the caller's pointers through its slot maps and, where the plan
+// has double-buffered buffers, their parity; `launch(kargs, group)` is the plan's kernel launch.
+template<typename Plan, typename Launch>
+int execute_groups(const Plan& p, const parity_cfg* parity, void* const* fptr, int nf,
+                   void* const* bptr, int nb, Launch&& launch)
+{
+    if (total_tiles(p.groups) == 0) return GHX_OK;
+    if (nf <= p.max_field_slot || nb <= p.max_buf_slot)
+        throw invalid("pointer arrays do not cover the plan's slots");
+    int rc = GHX_OK;
+    for (size_t g = 0; rc == GHX_OK && g < p.groups.size(); ++g)
+    {
+        const auto& grp = p.groups[g];
+        if (grp.n_tiles == 0) continue;
+        if (!grp.dev.segs && !grp.dev.recs)
+            throw hip_error("plan has no device tables (no HIP device at creation)");
+        kargs a{};
+        a.segs = grp.dev.segs;
+        a.tile_seg = grp.dev.tiles;
+        a.tile_recs = grp.dev.recs;
+        a.n_tiles = grp.n_tiles;
+        fill_slots(a.field_ptr, fptr, grp.fmap, p.max_field_slot + 1, "field");
+        fill_slots(a.buf_ptr, bptr, grp.bmap, p.max_buf_slot + 1, "buffer");
+        if (parity) parity->apply(a, grp.bmap, p.max_buf_slot + 1);
+        rc = launch(a, grp);
+    }
+    return rc;
+}
+}  // namespace
+
 void fill_slots(uint64_t* dst, void* const* src, const std::vector<int32_t>& map, int n_identity,
                 const char* what)
 {
@@ -313,7 +369,6 @@ void fill_slots(uint64_t* dst, void* const* src, const std::vector<int32_t>& map
         dst[i] = reinterpret_cast<uint64_t>(p);
     }
 }
-}  // namespace
 
 void device_tables::release()
 {
@@ -529,7 +584,8 @@ splan::splan(const ghx_pack_entry* entries, int n_entries, int dir) : direction(
         gb.resize(segs.size(), en.buffer_slot);
         bytes += off - en.buffer_offset;
     }
-    build(segs, gf, gb);
+    n_segments = int32_t(segs.size());
+    groups = build_groups(segs, gf, gb, direction);
 }
 
 splan::splan(std::vector<seg_s> segs, const std::vector<int32_t>& gf, const std::vector<int32_t>& gb,
@@ -546,74 +602,16 @@ splan::splan(std::vector<seg_s> segs, const std::vector<int32_t>& gf, const std:
         max_buf_slot = std::max(max_buf_slot, gb[k]);
     }
     bytes = nbytes;
-    build(segs, gf, gb);
-}
-
-void splan::build(const std::vector<seg_s>& segs, const std::vector<int32_t>& gf,
-                  const std::vector<int32_t>& gb)
-{
     n_segments = int32_t(segs.size());
-    const slot_partition part = partition_slots(gf, gb);
-    for (size_t g = 0; g < part.segs.size(); ++g)
-    {
-        std::vector<seg_s> gs;
-        for (uint32_t k : part.segs[g])
-        {
-            seg_s x = segs[k];
-            x.field_slot = uint16_t(part.lf[k]);
-            x.buf_slot = uint16_t(part.lb[k]);
-            gs.push_back(x);
-        }
-        std::vector<uint32_t> tiles = build_tiles(gs, direction);
-        if (g == 0)
-        {
-            n_tiles = uint32_t(tiles.size() / 2);
-            host_segs = gs;
-            host_tiles = tiles;
-            fmap = part.fmap[0];
-            bmap = part.bmap[0];
-            upload(dev, gs, tiles);
-            continue;
-        }
-        auto grp = std::make_unique<slot_group<seg_s>>();
-        grp->fmap = part.fmap[g];
-        grp->bmap = part.bmap[g];
-        grp->n_tiles = uint32_t(tiles.size() / 2);
-        grp->host_segs = gs;
-        upload(grp->dev, gs, tiles);
-        more.push_back(std::move(grp));
-    }
-}
-
-uint32_t splan::total_tiles() const
-{
-    uint32_t t = n_tiles;
-    for (const auto& g : more) t += g->n_tiles;
-    return t;
+    groups = build_groups(segs, gf, gb, direction);
 }
 
 int splan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
 {
-    if (total_tiles() == 0) return GHX_OK;
-    if (nf <= max_field_slot || nb <= max_buf_slot) throw invalid("pointer arrays do not cover the plan's slots");
-    auto run = [&](const device_tables& dt, uint32_t nt, const std::vector<int32_t>& fm,
-                   const std::vector<int32_t>& bm) {
-        if (nt == 0) return int(GHX_OK);
-        if (!dt.segs) throw hip_error("plan has no device tables (no HIP device at creation)");
-        kargs a{};
-        a.segs = dt.segs;
-        a.tile_seg = dt.tiles;
-        a.tile_recs = dt.recs;
-        a.n_tiles = nt;
-        fill_slots(a.field_ptr, fptr, fm, max_field_slot + 1, "field");
-        fill_slots(a.buf_ptr, bptr, bm, max_buf_slot + 1, "buffer");
-        parity.apply(a, bm, max_buf_slot + 1);
-        return launch_structured(a, direction, stream, grid_for_tiles(nt));
-    };
-    int rc = run(dev, n_tiles, fmap, bmap);
-    for (size_t g = 0; rc == GHX_OK && g < more.size(); ++g)
-        rc = run(more[g]->dev, more[g]->n_tiles, more[g]->fmap, more[g]->bmap);
-    return rc;
+    return execute_groups(*this, &parity, fptr, nf, bptr, nb,
+                          [&](const kargs& a, const launch_group<seg_s>&) {
+                              return launch_structured(a, direction, stream, grid_for_tiles(a.n_tiles));
+                          });
 }
 
 void finish_segment(seg_s& s)
@@ -738,44 +736,33 @@ xplan::xplan(std::vector<xseg> bx) : boxes(std::move(bx))
         bytes += b.bytes();
     }
     n_records = int32_t(boxes.size());
-    const slot_partition part = partition_slots(gf, gb);
-    for (size_t g = 0; g < part.segs.size(); ++g)
+    slot_partition part = partition_slots(gf, gb);
+    groups = std::vector<launch_group<seg_x>>(part.segs.size());
+    for (size_t g = 0; g < groups.size(); ++g)
     {
-        auto grp = std::make_unique<group>();
-        grp->fmap = part.fmap[g];
-        grp->bmap = part.bmap[g];
+        launch_group<seg_x>& grp = groups[g];
+        grp.fmap = std::move(part.fmap[g]);
+        grp.bmap = std::move(part.bmap[g]);
         for (uint32_t k : part.segs[g])
-            make_tile_records(grp->host, boxes[k], uint16_t(part.lf[k]), uint16_t(part.lb[k]));
-        n_tiles += uint32_t(grp->host.size());
-        if (!grp->host.empty() && have_device())
+            make_tile_records(grp.host_segs, boxes[k], uint16_t(part.lf[k]), uint16_t(part.lb[k]));
+        grp.n_tiles = uint32_t(grp.host_segs.size());
+        n_tiles += grp.n_tiles;
+        if (grp.n_tiles && have_device())
         {
-            const size_t rb = grp->host.size() * sizeof(seg_x);
-            if (hipMalloc(&grp->dev.recs, rb) != hipSuccess) throw hip_error("hipMalloc(transformed records)");
-            if (hipMemcpy(grp->dev.recs, grp->host.data(), rb, hipMemcpyHostToDevice) != hipSuccess)
+            const size_t rb = grp.host_segs.size() * sizeof(seg_x);
+            if (hipMalloc(&grp.dev.recs, rb) != hipSuccess) throw hip_error("hipMalloc(transformed records)");
+            if (hipMemcpy(grp.dev.recs, grp.host_segs.data(), rb, hipMemcpyHostToDevice) != hipSuccess)
                 throw hip_error("hipMemcpy(transformed records)");
         }
-        groups.push_back(std::move(grp));
     }
 }
 
 int xplan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
 {
-    if (n_tiles == 0) return GHX_OK;
-    if (nf <= max_field_slot || nb <= max_buf_slot) throw invalid("pointer arrays do not cover the plan's slots");
-    int rc = GHX_OK;
-    for (size_t g = 0; rc == GHX_OK && g < groups.size(); ++g)
-    {
-        const group& grp = *groups[g];
-        if (grp.host.empty()) continue;
-        if (!grp.dev.recs) throw hip_error("plan has no device tables (no HIP device at creation)");
-        kargs a{};
-        a.tile_recs = grp.dev.recs;
-        a.n_tiles = uint32_t(grp.host.size());
-        fill_slots(a.field_ptr, fptr, grp.fmap, max_field_slot + 1, "field");
-        fill_slots(a.buf_ptr, bptr, grp.bmap, max_buf_slot + 1, "buffer");
-        rc = launch_unpack_x(a, stream, grid_for_tiles(a.n_tiles));
-    }
-    return rc;
+    return execute_groups(*this, nullptr, fptr, nf, bptr, nb,
+                          [&](const kargs& a, const launch_group<seg_x>&) {
+                              return launch_unpack_x(a, stream, grid_for_tiles(a.n_tiles));
+                          });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -866,10 +853,10 @@ cs_self_plan::cs_self_plan(const std::vector<seg_s>& pack, const std::vector<seg
         slot(b.src_slot, b.dst.buf_slot);
     }
     // the fused self exchange's tile size, as ghx_exchange_self uses it
-    const uint32_t saved = g_tune.tile_bytes;
-    g_tune.tile_bytes = g_tune.self_tile_bytes;
-    build_pairs(std::move(p), std::move(q));
-    g_tune.tile_bytes = saved;
+    {
+        const tile_bytes_scope tile(g_tune.self_tile_bytes);
+        build_pairs(std::move(p), std::move(q));
+    }
     build_tiles_x(boxes, true);
     upload("self");
 }
@@ -1107,82 +1094,27 @@ uplan::uplan(const ghx_upack_entry* entries, int n_entries, int dir) : direction
                 for (int64_t i = 0; i < p.n; ++i) dst[i] = int32_t(p.lids[i]);
             }
         }
-        if (hipMalloc(&dev.lids, lid_bytes) != hipSuccess) throw hip_error("hipMalloc(lids)");
-        if (hipMemcpy(dev.lids, host.data(), lid_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        if (hipMalloc(&lid_store.lids, lid_bytes) != hipSuccess) throw hip_error("hipMalloc(lids)");
+        if (hipMemcpy(lid_store.lids, host.data(), lid_bytes, hipMemcpyHostToDevice) != hipSuccess)
             throw hip_error("hipMemcpy(lids)");
-        for (auto& p : pend) segs[p.seg].lids = static_cast<char*>(dev.lids) + p.off;
+        for (auto& p : pend) segs[p.seg].lids = static_cast<char*>(lid_store.lids) + p.off;
     }
-    const slot_partition part = partition_slots(gf, gb);
-    for (size_t g = 0; g < part.segs.size(); ++g)
-    {
-        std::vector<seg_u> gs;
-        for (uint32_t k : part.segs[g])
-        {
-            seg_u x = segs[k];
-            x.field_slot = uint16_t(part.lf[k]);
-            x.buf_slot = uint16_t(part.lb[k]);
-            gs.push_back(x);
-        }
-        std::vector<uint32_t> tiles = build_tiles(gs, direction);
-        if (g == 0)
-        {
-            n_tiles = uint32_t(tiles.size() / 2);
-            host_segs = gs;
-            fmap = part.fmap[0];
-            bmap = part.bmap[0];
-            void* keep = dev.lids;
-            dev.lids = nullptr;  // upload() releases; re-attach after (the groups share it)
-            upload(dev, gs, tiles);
-            dev.lids = keep;
-            continue;
-        }
-        auto grp = std::make_unique<slot_group<seg_u>>();
-        grp->fmap = part.fmap[g];
-        grp->bmap = part.bmap[g];
-        grp->n_tiles = uint32_t(tiles.size() / 2);
-        grp->host_segs = gs;
-        upload(grp->dev, gs, tiles);
-        more.push_back(std::move(grp));
-    }
-}
-
-uint32_t uplan::total_tiles() const
-{
-    uint32_t t = n_tiles;
-    for (const auto& g : more) t += g->n_tiles;
-    return t;
+    groups = build_groups(segs, gf, gb, direction);
 }
 
 int uplan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
 {
-    if (total_tiles() == 0) return GHX_OK;
-    if (nf <= max_field_slot || nb <= max_buf_slot) throw invalid("pointer arrays do not cover the plan's slots");
-    auto run = [&](const device_tables& dt, uint32_t nt, const std::vector<int32_t>& fm,
-                   const std::vector<int32_t>& bm, const std::vector<seg_u>& hs) {
-        if (nt == 0) return int(GHX_OK);
-        if (!dt.segs) throw hip_error("plan has no device tables (no HIP device at creation)");
-        kargs a{};
-        a.segs = dt.segs;
-        a.tile_seg = dt.tiles;
-        a.tile_recs = dt.recs;
-        a.n_tiles = nt;
-        fill_slots(a.field_ptr, fptr, fm, max_field_slot + 1, "field");
-        fill_slots(a.buf_ptr, bptr, bm, max_buf_slot + 1, "buffer");
-        parity.apply(a, bm, max_buf_slot + 1);
+    return execute_groups(*this, &parity, fptr, nf, bptr, nb, [&](const kargs& a, const launch_group<seg_u>& grp) {
         // the run-path kernel when every segment qualifies with these pointers: flagged by the
         // planner, whole 16-B chunks per tile, 16-B aligned buffer ranges (both copies of a
         // double-buffered one), field base aligned to L
-        bool runs = !hs.empty();
-        for (const seg_u& s : hs)
+        bool runs = !grp.host_segs.empty();
+        for (const seg_u& s : grp.host_segs)
             runs = runs && s.runs && s.tile_bytes % 16 == 0 &&
                    (a.buf_ptr[s.buf_slot] + s.buf_off) % 16 == 0 && a.dbl_off[s.buf_slot] % 16 == 0 &&
                    a.field_ptr[s.field_slot] % s.row_bytes == 0;
-        return launch_unstructured(a, direction, stream, grid_for_tiles(nt), runs);
-    };
-    int rc = run(dev, n_tiles, fmap, bmap, host_segs);
-    for (size_t g = 0; rc == GHX_OK && g < more.size(); ++g)
-        rc = run(more[g]->dev, more[g]->n_tiles, more[g]->fmap, more[g]->bmap, more[g]->host_segs);
-    return rc;
+        return launch_unstructured(a, direction, stream, grid_for_tiles(a.n_tiles), runs);
+    });
 }
 
 }  // namespace ghx

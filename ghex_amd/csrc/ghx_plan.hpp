@@ -45,6 +45,14 @@ void upload_pair_records(device_tables& dt, const std::vector<seg_s>& primary,
                          const std::vector<seg_s>& companion, const std::vector<uint32_t>& tiles);
 uint64_t add_box_segments(std::vector<seg_s>& out, const ghx_field_desc& f, const ghx_box& box,
                           uint16_t field_slot, uint16_t buf_slot, uint64_t buf_off);
+// plans built inside its scope tile their long rows by `bytes` (g_tune.tile_bytes, put back on
+// every exit)
+struct tile_bytes_scope
+{
+    const uint32_t saved = g_tune.tile_bytes;
+    explicit tile_bytes_scope(uint32_t bytes) { g_tune.tile_bytes = bytes; }
+    ~tile_bytes_scope() { g_tune.tile_bytes = saved; }
+};
 // the derived members of a segment built by hand (divisors, vector width, addressing form) from
 // its offsets, strides, extents, row length and byte count
 void finish_segment(seg_s& s);
@@ -55,14 +63,32 @@ void finish_segment(seg_s& s);
 // entry order, each with its own slot maps (local slot -> the caller's slot) and tables, and
 // executes as one launch per group on the same stream. The reference has no such limit
 // (include/ghex/communication_object.hpp:1003-1067 allocates any number of buffers).
+// Every plan holds all its groups in `groups`; a plan without segments has one empty group.
 template<typename Seg>
-struct slot_group
+struct launch_group
 {
-    std::vector<int32_t> fmap, bmap;  // local slot -> caller slot; empty: identity
+    std::vector<int32_t> fmap, bmap;   // local slot -> caller slot; empty: identity
     uint32_t n_tiles = 0;
-    std::vector<Seg> host_segs;
+    std::vector<Seg> host_segs;        // local slots (xplan: its tile records)
+    std::vector<uint32_t> host_tiles;  // the tile table (pair records)
     device_tables dev;
 };
+template<typename Seg>
+uint32_t total_tiles(const std::vector<launch_group<Seg>>& groups)
+{
+    uint32_t t = 0;
+    for (const auto& g : groups) t += g.n_tiles;
+    return t;
+}
+template<typename Seg>
+bool grouped(const std::vector<launch_group<Seg>>& groups)
+{
+    return groups.size() > 1 || !groups[0].fmap.empty() || !groups[0].bmap.empty();
+}
+// Fill a launch's pointer slots from the caller's arrays through a group's maps (empty: the
+// first n_identity pointers as they are); `what` names the pointers in the null refusal.
+void fill_slots(uint64_t* dst, void* const* src, const std::vector<int32_t>& map, int n_identity,
+                const char* what);
 
 // structured fused plan
 struct splan
@@ -70,25 +96,19 @@ struct splan
     int direction = 0;
     uint64_t bytes = 0;
     int32_t n_segments = 0;
-    uint32_t n_tiles = 0;      // the first launch group's (the whole plan's when not grouped)
     uint32_t tile_bytes = kTileBytes;
     int max_field_slot = -1, max_buf_slot = -1;  // caller slots
-    std::vector<seg_s> host_segs;                // the first group's, local slots
-    std::vector<uint32_t> host_tiles;            // the first group's tile table (pair records)
-    device_tables dev;
-    std::vector<int32_t> fmap, bmap;             // the first group's slot maps (empty: identity)
-    std::vector<std::unique_ptr<slot_group<seg_s>>> more;  // further launch groups
+    std::vector<launch_group<seg_s>> groups;
     parity_cfg parity;                           // double-buffered buffers (direct exchange)
-    bool grouped() const { return !fmap.empty() || !bmap.empty() || !more.empty(); }
-    uint32_t total_tiles() const;
+    bool grouped() const { return ghx::grouped(groups); }
+    uint32_t total_tiles() const { return ghx::total_tiles(groups); }
+    // the one group of a plan that is not grouped() (the fused launches take no other)
+    const launch_group<seg_s>& first() const { return groups[0]; }
     splan(const ghx_pack_entry* entries, int n_entries, int direction);
     // from ready segments (cubed sphere: rotated spaces that keep contiguous rows): gf / gb are
     // the caller's field / buffer slot of each segment, `bytes` the buffer bytes they cover
     splan(std::vector<seg_s> segs, const std::vector<int32_t>& gf, const std::vector<int32_t>& gb,
           uint64_t bytes, int direction);
-    // launch groups, tile tables and device tables of the plan's segments (both constructors)
-    void build(const std::vector<seg_s>& segs, const std::vector<int32_t>& gf,
-               const std::vector<int32_t>& gb);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
 
@@ -102,13 +122,7 @@ struct xplan
     uint32_t n_tiles = 0;      // of all groups
     int max_field_slot = -1, max_buf_slot = -1;  // caller slots
     std::vector<xseg> boxes;
-    struct group
-    {
-        std::vector<int32_t> fmap, bmap;
-        std::vector<seg_x> host;
-        device_tables dev;     // dev.recs: the records
-    };
-    std::vector<std::unique_ptr<group>> groups;
+    std::vector<launch_group<seg_x>> groups;  // host_segs: the tile records, dev.recs on the device
     explicit xplan(std::vector<xseg> boxes);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
@@ -191,19 +205,26 @@ struct uplan
     int direction = 0;
     uint64_t bytes = 0;
     int32_t n_segments = 0;
-    uint32_t n_tiles = 0;
     uint32_t tile_bytes = kTileBytes;
     int max_field_slot = -1, max_buf_slot = -1;
-    device_tables dev;
-    std::vector<seg_u> host_segs;  // for the launch-time choice of the run-path kernel
-    std::vector<int32_t> fmap, bmap;
-    std::vector<std::unique_ptr<slot_group<seg_u>>> more;
+    std::vector<launch_group<seg_u>> groups;  // host_segs: the launch-time choice of the run path
+    device_tables lid_store;                  // lids: the index lists of every group's segments
     parity_cfg parity;
-    bool grouped() const { return !fmap.empty() || !bmap.empty() || !more.empty(); }
-    uint32_t total_tiles() const;
+    bool grouped() const { return ghx::grouped(groups); }
+    uint32_t total_tiles() const { return ghx::total_tiles(groups); }
     uplan(const ghx_upack_entry* entries, int n_entries, int direction);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
+
+// The per-call entry points' plans, cached by content (ghx_cache.cpp): the plan of the call's
+// descriptor and spaces, or index list, is built on first use and executed on `stream`.
+int run_structured(const ghx_field_desc& f, const ghx_box* boxes, int n, int dir, void* field,
+                   void* buffer, void* stream);
+int run_cs_unpack(const ghx_field_desc& f, const ghx_cs_item& cs, const ghx_box* local,
+                  const ghx_box* global, const int32_t* tiles, int n, void* field, void* buffer,
+                  void* stream);
+int run_unstructured(const ghx_udata_desc& d, const void* lids, int32_t lid_bytes, int64_t n,
+                     int dir, void* values, void* buffer, void* stream);
 }  // namespace ghx
 
 // opaque handles

@@ -115,6 +115,52 @@ def case_entry(case: Case, offsets=None):
     return entry(field_desc(case, offsets), [box])
 
 
+# More slots than two launches carry (64 each): 130 distinct field and buffer slots are three
+# launch groups of 64, 64 and 2, shared by tests/test_plan_addressing.py (host) and
+# tests/test_gpu_fuzz.py (device). Entry k: field slot k, buffer slot N_SLOTS - 1 - k.
+N_SLOTS = 130
+SLOT_BOX = ((2, 1, 0), (3, 2, 1))  # x, y, z: a[0:2, 1:3, 2:4] of a (z, y, x) array
+SLOT_BOX_BYTES = 32
+U_CELLS, U_LEVELS, U_LIDS = 10, 2, 4
+
+
+def many_slot_entries():
+    """N_SLOTS structured entries, each the 2x2x2 box SLOT_BOX of its own unit-stride 4x4x4 fp32
+    field; returns (ghx_pack_entry array, keep-alive)."""
+    from ghex_amd import _ghx
+    case = Case("S", 4, L3, (4, 16, 64), (4, 4, 4), (8, 2, 4, 3, 1))
+    desc = field_desc(case)
+    for k in range(3):
+        desc.extents[k] = 4
+    ents, keep = [], []
+    for k in range(N_SLOTS):
+        e, arr = entry(desc, [SLOT_BOX], k, N_SLOTS - 1 - k)
+        ents.append(e)
+        keep.append(arr)
+    return (_ghx.PackEntry * N_SLOTS)(*ents), keep
+
+
+def many_slot_lids():
+    """Entry k's U_LIDS distinct cells of U_CELLS, in a seeded random order: (N_SLOTS, U_LIDS)."""
+    rng = np.random.default_rng(130)
+    return np.stack([rng.permutation(U_CELLS)[:U_LIDS] for _ in range(N_SLOTS)]).astype(np.int64)
+
+
+def many_slot_uentries(lids):
+    """N_SLOTS unstructured entries over many_slot_lids(): fp32 values of U_LEVELS levels,
+    levels first (one 8-B row per cell); returns the ghx_upack_entry array (lids kept by caller)."""
+    from ghex_amd import _ghx
+    ents = []
+    for k in range(N_SLOTS):
+        e = _ghx.UPackEntry()
+        e.data.elem_size, e.data.levels, e.data.levels_first = 4, U_LEVELS, 1
+        e.data.index_stride, e.data.level_stride = U_LEVELS, 1
+        e.field_slot, e.buffer_slot, e.buffer_offset = k, N_SLOTS - 1 - k, 0
+        e.lids, e.n_lids = _ghx.i64_ptr(lids[k]), U_LIDS
+        ents.append(e)
+    return (_ghx.UPackEntry * N_SLOTS)(*ents)
+
+
 class Plan:
     """A ghx_plan handle (pack 0 / unpack 1) destroyed on exit."""
 

@@ -83,17 +83,14 @@ void run(const config& cfg, const int* layout, int elem, int nc, int vector, int
         }
     };
     if (ex->sunpack)
-    {
-        replay_s(ex->sunpack->host_segs, ex->sunpack->fmap, ex->sunpack->bmap);
-        for (const auto& g : ex->sunpack->more) replay_s(g->host_segs, g->fmap, g->bmap);
-    }
+        for (const auto& g : ex->sunpack->groups) replay_s(g.host_segs, g.fmap, g.bmap);
     // transformed tile records, as k_unpack_x walks them: field order, transposed buffer reads
     if (ex->xunpack)
         for (const auto& g : ex->xunpack->groups)
-            for (const seg_x& s : g->host)
+            for (const seg_x& s : g.host_segs)
             {
-                const int fs = g->fmap.empty() ? s.field_slot : g->fmap[s.field_slot];
-                const int bs = g->bmap.empty() ? s.buf_slot : g->bmap[s.buf_slot];
+                const int fs = g.fmap.empty() ? s.field_slot : g.fmap[s.field_slot];
+                const int bs = g.bmap.empty() ? s.buf_slot : g.bmap[s.buf_slot];
                 CHECK(s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3] <= 4096);
                 CHECK((1 << s.elog2) == elem);
                 replay_tile(s, x_tile_elems, [&](const uint32_t (&c)[4], int64_t off) {

@@ -205,6 +205,67 @@ def test_more_slots_than_one_launch_holds():
               "periodic": (1, 1, 1), "fields": fields, "mixed": False, "seed": 64})
 
 
+def test_three_launch_groups_execute_bit_exact():
+    """130 distinct field and buffer slots (tests/addressing_cases.py many_slot_*): three launch
+    groups, the third being the second of the further groups. The structured plan packs 130
+    fields' boxes into 130 buffers and unpacks them into zeroed fields through ghx_plan_execute,
+    the unstructured plan (narrow device index lists, 2 levels, fp32) gathers and scatters the
+    same way through ghx_uplan_execute; every byte equals numpy's."""
+    import ctypes
+    import torch
+    from ghex_amd import _ghx
+    from tests import addressing_cases as A
+    N = A.N_SLOTS
+    rng = np.random.default_rng(131)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(create, execute, destroy, ents, direction, fields, bufs):
+        h = ctypes.c_void_p()
+        _ghx.call(create, ents, N, direction, ctypes.byref(h))
+        try:
+            fp = _ghx.ptr_array([fields[k].data_ptr() for k in range(N)])
+            bp = _ghx.ptr_array([bufs[b].data_ptr() for b in range(N)])
+            _ghx.call(execute, h, fp, N, bp, N, stream)
+            torch.cuda.synchronize()
+        finally:
+            getattr(_ghx.lib(), destroy)(h)
+
+    def same(t, a):
+        np.testing.assert_array_equal(t.cpu().numpy().view(np.uint8), a.view(np.uint8))
+
+    # structured: field k's box in buffer N - 1 - k
+    (x0, y0, z0), (x1, y1, z1) = A.SLOT_BOX
+    a = rng.standard_normal((N, 4, 4, 4)).astype(np.float32)
+    box = a[:, z0:z1 + 1, y0:y1 + 1, x0:x1 + 1]
+    exp_buf = box.reshape(N, -1)[::-1].copy()
+    exp_field = np.zeros_like(a)
+    exp_field[:, z0:z1 + 1, y0:y1 + 1, x0:x1 + 1] = box
+    ents, keep = A.many_slot_entries()
+    fields = torch.from_numpy(a).cuda()
+    bufs = torch.zeros((N, A.SLOT_BOX_BYTES // 4), dtype=torch.float32, device="cuda")
+    run("ghx_plan_create", "ghx_plan_execute", "ghx_plan_destroy", ents, 0, fields, bufs)
+    same(bufs, exp_buf)
+    back = torch.zeros_like(fields)
+    run("ghx_plan_create", "ghx_plan_execute", "ghx_plan_destroy", ents, 1, back, bufs)
+    same(back, exp_field)
+
+    # unstructured: values (cells, levels), entry k's cells in buffer N - 1 - k
+    lids = A.many_slot_lids()
+    v = rng.standard_normal((N, A.U_CELLS, A.U_LEVELS)).astype(np.float32)
+    rows = np.take_along_axis(v, lids[:, :, None], axis=1)
+    exp_buf = rows.reshape(N, -1)[::-1].copy()
+    exp_vals = np.zeros_like(v)
+    np.put_along_axis(exp_vals, lids[:, :, None], rows, axis=1)
+    uents = A.many_slot_uentries(lids)
+    vals = torch.from_numpy(v).cuda()
+    bufs = torch.zeros((N, A.U_LIDS * A.U_LEVELS), dtype=torch.float32, device="cuda")
+    run("ghx_uplan_create", "ghx_uplan_execute", "ghx_uplan_destroy", uents, 0, vals, bufs)
+    same(bufs, exp_buf)
+    back = torch.zeros_like(vals)
+    run("ghx_uplan_create", "ghx_uplan_execute", "ghx_uplan_destroy", uents, 1, back, bufs)
+    same(back, exp_vals)
+
+
 def test_receive_only_field_slot_in_mixed_exchange():
     """Seed 249 (found by the soak, tools/fuzz_soak.py): 2 ranks x 12-15 thin domains, a y- halo
     only and no y periodicity, so the highest field slot of a rank belongs to a domain that only

@@ -50,7 +50,24 @@ def test_errors_are_reported_not_thrown(ghx):
 @pytest.mark.parametrize("key,good,bad", [("fast_addr", [0, 1], [-1, 2]),
                                            ("pack_tile_rows", [0, 64, 65536], [-1, 63, 65537]),
                                            ("unpack_tile_rows", [0, 512], [32, 1 << 20]),
-                                           ("tile_records", [0, 1], [2])])
+                                           ("tile_records", [0, 1], [2]),
+                                           ("order", [0, 1], [-1, 2]),
+                                           ("mixed_always", [0, 1], [-1, 2]),
+                                           ("xcd_pair", [0, 1], [-1, 2]),
+                                           ("urun", [0, 1], [-1, 2]),
+                                           ("short_pol", [0, 3], [-1, 4]),
+                                           ("x_tile_elems", [32, 4096], [31, 4097]),
+                                           ("u_tile_rows", [1, 2**31 - 1], [0, -1]),
+                                           ("u_run_tile_rows", [4, 2**31 - 1], [3, 0]),
+                                           ("small_row_bytes", [1, 2**31 - 1], [0, -1]),
+                                           ("grid_cap", [0, 2**31 - 1], [-1, -2**31]),
+                                           ("small_tile_rows", [0, 64, 65536], [-1, 63, 65537]),
+                                           ("unpack_tile_rows", [64, 65536], [-1, 63, 65537]),
+                                           ("tile_bytes", [1024, 1 << 20], [0, 512, 1025, 1 << 21]),
+                                           ("self_tile_bytes", [1024, 1 << 20], [0, 512, 1536, 1 << 21]),
+                                           ("u_tile_bytes", [1024, 1 << 20], [0, 512, 3000, -1024]),
+                                           ("unpack_tile_bytes", [0, 1024, 1 << 20],
+                                            [-1, 512, 3072, 1 << 21])])
 def test_tuning_knobs_validate_their_range(ghx, key, good, bad):
     """ghx_tune accepts each knob's documented range and refuses the rest with a message naming
     the knob (unknown keys too); `reset` restores the defaults."""

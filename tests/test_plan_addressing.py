@@ -119,3 +119,47 @@ def test_plan_segment_argument_checks_and_order(ghx):
         assert L.ghx_plan_segment(None, 0, ctypes.byref(s)) == -1
     finally:
         assert L.ghx_plan_destroy(h) == 0
+
+
+def test_three_launch_groups_report_every_segment_in_order(ghx):
+    """130 distinct field and buffer slots are three launch groups (64, 64, 2): ghx_plan_segment
+    returns all 130 segments in plan order with the caller's slots, ghx_plan_info the segments
+    and the tiles summed over the groups, and index 130 is refused. The unstructured plan of 130
+    slots reports its bytes, segments and tiles the same way."""
+    L = ghx.lib()
+    nb, n, nt = ctypes.c_uint64(), ctypes.c_int32(), ctypes.c_int32()
+    ents, keep = A.many_slot_entries()
+    one = ctypes.c_void_p()
+    assert L.ghx_plan_create(ents, 1, 0, ctypes.byref(one)) == 0, L.ghx_last_error()
+    assert L.ghx_plan_info(one, None, None, ctypes.byref(nt)) == 0
+    assert L.ghx_plan_destroy(one) == 0
+    tiles_each = nt.value
+    assert tiles_each == 1
+    for direction in (0, 1):
+        h = ctypes.c_void_p()
+        assert L.ghx_plan_create(ents, A.N_SLOTS, direction, ctypes.byref(h)) == 0, L.ghx_last_error()
+        try:
+            assert L.ghx_plan_info(h, ctypes.byref(nb), ctypes.byref(n), ctypes.byref(nt)) == 0
+            assert (nb.value, n.value, nt.value) == (A.N_SLOTS * A.SLOT_BOX_BYTES, A.N_SLOTS,
+                                                     A.N_SLOTS * tiles_each)
+            s = ghx.SegmentInfo()
+            for k in range(A.N_SLOTS):
+                assert L.ghx_plan_segment(h, k, ctypes.byref(s)) == 0
+                assert (s.field_slot, s.buffer_slot) == (k, A.N_SLOTS - 1 - k)
+                assert (s.field_off, s.buf_off, s.bytes) == (24, 0, A.SLOT_BOX_BYTES)
+                assert A.seg_facts(s) == (8, 2, 4, 3, 1)
+            assert L.ghx_plan_segment(h, A.N_SLOTS, ctypes.byref(s)) == -1
+            assert b"out of range" in L.ghx_last_error()
+        finally:
+            assert L.ghx_plan_destroy(h) == 0
+    lids = A.many_slot_lids()
+    uents = A.many_slot_uentries(lids)
+    for direction in (0, 1):
+        h = ctypes.c_void_p()
+        assert L.ghx_uplan_create(uents, A.N_SLOTS, direction, ctypes.byref(h)) == 0, L.ghx_last_error()
+        try:
+            assert L.ghx_uplan_info(h, ctypes.byref(nb), ctypes.byref(n), ctypes.byref(nt)) == 0
+            assert (nb.value, n.value, nt.value) == (A.N_SLOTS * A.U_LIDS * A.U_LEVELS * 4,
+                                                     A.N_SLOTS, A.N_SLOTS)
+        finally:
+            assert L.ghx_uplan_destroy(h) == 0

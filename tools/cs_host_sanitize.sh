@@ -17,8 +17,8 @@ C="$ROOT/ghex_amd/csrc"
 PROGS="cs_host_check cs_self_host_check cs_put_host_check"
 OBJS=""
 PIDS=""
-for f in ghx_kernels.hip ghx_epochs.hip ghx_copier.hip ghx_plan.cpp ghx_abi.cpp ghx_pattern.cpp \
-         ghx_cubed_sphere.cpp ghx_upattern.cpp ghx_pipeline.cpp; do
+for f in ghx_kernels.hip ghx_epochs.hip ghx_copier.hip ghx_plan.cpp ghx_exchange.cpp ghx_cache.cpp ghx_abi.cpp \
+         ghx_pattern.cpp ghx_cubed_sphere.cpp ghx_upattern.cpp ghx_pipeline.cpp; do
   o="$S/${f%.*}.o"
   if [ "${f##*.}" = hip ]; then x="-munsafe-fp-atomics"; else x=""; fi
   $HIPCC $FLAGS $x -c "$C/$f" -o "$o" &
