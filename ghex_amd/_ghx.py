@@ -48,6 +48,15 @@ class UPackEntry(ctypes.Structure):
                 ("buffer_offset", c_u64), ("lids", ctypes.POINTER(c_i64)), ("n_lids", c_i64)]
 
 
+class USegmentInfo(ctypes.Structure):
+    _fields_ = [("field_off", c_i64), ("buf_off", c_u64), ("index_stride_b", c_i64),
+                ("level_stride_b", c_i64), ("bytes", ctypes.c_uint32),
+                ("row_bytes", ctypes.c_uint32), ("tile_bytes", ctypes.c_uint32),
+                ("n", ctypes.c_uint32), ("field_slot", c_i32), ("buffer_slot", c_i32),
+                ("mode", c_i32), ("wlog2", c_i32), ("lid64", c_i32), ("runs", c_i32),
+                ("fpol", c_i32)]
+
+
 class RegularDomain(ctypes.Structure):
     _fields_ = [("id", c_i32), ("rank", c_i32), ("first", c_i32 * 3), ("last", c_i32 * 3)]
 
@@ -86,6 +95,7 @@ _SIGS = {
     "ghx_uplan_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_uplan_destroy": (c_i32, [c_vp]),
     "ghx_uplan_info": (c_i32, [c_vp, P(c_u64), P(c_i32), P(c_i32)]),
+    "ghx_uplan_segment": (c_i32, [c_vp, c_i32, P(USegmentInfo)]),
     "ghx_regular_halo_boxes": (c_i32, [c_i32, P(c_i32), P(c_i32), P(c_i32), P(c_i32), P(c_i32),
                                        P(c_i32), P(Box), P(Box), c_i32, P(c_i32)]),
     "ghx_regular_pattern_create": (c_i32, [c_i32, P(RegularDomain), c_i32, P(c_i32), P(c_i32),

@@ -292,6 +292,39 @@ int ghx_uplan_info(const ghx_uplan* plan, uint64_t* bytes, int32_t* n_segments, 
     });
 }
 
+int ghx_uplan_segment(const ghx_uplan* plan, int32_t k, ghx_usegment_info* out)
+{
+    return guarded([&] {
+        check_ptr(plan, "plan");
+        check_ptr(out, "out");
+        if (k < 0 || k >= plan->n_segments) throw invalid("segment index out of range");
+        // the host copies of the launch groups, in plan order (as ghx_plan_segment)
+        size_t i = size_t(k), g = 0;
+        while (g < plan->groups.size() && i >= plan->groups[g].host_segs.size())
+            i -= plan->groups[g++].host_segs.size();
+        if (g == plan->groups.size()) throw invalid("segment index out of range");
+        const launch_group<seg_u>& grp = plan->groups[g];
+        const seg_u& s = grp.host_segs[i];
+        *out = ghx_usegment_info{};
+        out->field_off = s.field_off;
+        out->buf_off = s.buf_off;
+        out->index_stride_b = s.index_stride_b;
+        out->level_stride_b = s.level_stride_b;
+        out->bytes = s.bytes;
+        out->row_bytes = s.row_bytes;
+        out->tile_bytes = s.tile_bytes;
+        out->n = s.n;
+        out->field_slot = grp.fmap.empty() ? int32_t(s.field_slot) : grp.fmap[s.field_slot];
+        out->buffer_slot = grp.bmap.empty() ? int32_t(s.buf_slot) : grp.bmap[s.buf_slot];
+        out->mode = s.mode;
+        out->wlog2 = s.wlog2;
+        out->lid64 = s.lid64;
+        out->runs = s.runs;
+        out->fpol = s.fpol;
+        return GHX_OK;
+    });
+}
+
 // ----------------------------------------------------------------------------------- patterns
 int ghx_regular_halo_boxes(int32_t dim, const int32_t* global_first, const int32_t* global_last,
                            const int32_t* halos, const int32_t* periodic,

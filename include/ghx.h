@@ -242,6 +242,42 @@ int ghx_uplan_execute(const ghx_uplan* plan, void* const* field_ptrs, int32_t n_
 int ghx_uplan_destroy(ghx_uplan* plan);
 int ghx_uplan_info(const ghx_uplan* plan, uint64_t* bytes, int32_t* n_segments, int32_t* n_tiles);
 
+/* What the planner decided for one index-list segment (introspection only, the twin of
+ * ghx_plan_segment): the host copy of segment k of a plan, k in [0, n_segments) of
+ * ghx_uplan_info — the segments of all launch groups in plan order (entries, the pieces of a
+ * list split below 2^30 bytes). A segment moves `bytes` buffer bytes from buf_off on, as rows of
+ * `row_bytes` contiguous field bytes over `n` local indices. Buffer row r sits in the field at
+ * field_off + lid[i] * index_stride_b + l * level_stride_b, where by `mode`
+ *   0: i = r, l = 0 (one row per index: all its levels, or the one level of a split list);
+ *   1: i = r / levels, l = r % levels (levels first, strided levels; levels = bytes/row_bytes/n);
+ *   2: l = r / n, i = r % n (levels last).
+ * tile_bytes: the segment's workgroup tile, a whole number of rows. wlog2: log2 of the widest
+ * vector the planner allows (the launch narrows it by the pointers' alignment). lid64: the
+ * device index table holds int64 (some lid >= 2^31), else int32. runs: the segment qualifies for
+ * the run path (4/8-B rows adjacent in the field; 2: run-heavy), which a launch takes only when
+ * every segment of its group does and the pointers allow it. fpol: field-side cache policy (bit 0
+ * non-temporal loads, bit 1 sc1 stores). Slots are the caller's. Works on plans created without
+ * a device. k out of range: GHX_ERR_INVALID. */
+typedef struct ghx_usegment_info
+{
+    int64_t field_off;
+    uint64_t buf_off;
+    int64_t index_stride_b;
+    int64_t level_stride_b;
+    uint32_t bytes;
+    uint32_t row_bytes;
+    uint32_t tile_bytes;
+    uint32_t n;
+    int32_t field_slot;
+    int32_t buffer_slot;
+    int32_t mode;
+    int32_t wlog2;
+    int32_t lid64;
+    int32_t runs;
+    int32_t fpol;
+} ghx_usegment_info;
+int ghx_uplan_segment(const ghx_uplan* plan, int32_t k, ghx_usegment_info* out);
+
 /* ------------------------------------------------------------------------------------------
  * Patterns (setup time, host only): the producers of the pack inputs.
  * ------------------------------------------------------------------------------------------ */
