@@ -57,6 +57,23 @@ class USegmentInfo(ctypes.Structure):
                 ("fpol", c_i32)]
 
 
+class UPutEntry(ctypes.Structure):
+    _fields_ = [("data", UDataDesc), ("field_slot", c_i32), ("lids", ctypes.POINTER(c_i64)),
+                ("n_lids", c_i64)]
+
+
+class UPutSegmentInfo(ctypes.Structure):
+    _fields_ = [("src_field_off", c_i64), ("src_index_stride_b", c_i64),
+                ("src_level_stride_b", c_i64), ("dst_field_off", c_i64),
+                ("dst_index_stride_b", c_i64), ("dst_level_stride_b", c_i64),
+                ("first_index", c_i64), ("bytes", ctypes.c_uint32),
+                ("row_bytes", ctypes.c_uint32), ("tile_bytes", ctypes.c_uint32),
+                ("n", ctypes.c_uint32), ("message", c_i32), ("n_segments", c_i32),
+                ("src_slot", c_i32), ("dst_slot", c_i32), ("mode", c_i32), ("wlog2", c_i32),
+                ("src_lid64", c_i32), ("dst_lid64", c_i32), ("src_runs", c_i32),
+                ("dst_runs", c_i32)]
+
+
 class RegularDomain(ctypes.Structure):
     _fields_ = [("id", c_i32), ("rank", c_i32), ("first", c_i32 * 3), ("last", c_i32 * 3)]
 
@@ -171,6 +188,8 @@ _SIGS = {
     "ghx_cs_put_create": (c_i32, [P(PackEntry), c_i32, P(PackEntry), c_i32, P(CsItem),
                                   P(P(Box)), P(P(c_i32)), P(c_vp)]),
     "ghx_cs_put_info": (c_i32, [c_vp, P(c_i32), P(c_i32), P(c_i32)]),
+    "ghx_uput_create": (c_i32, [P(UPutEntry), P(UPutEntry), c_i32, P(c_vp)]),
+    "ghx_uput_segment": (c_i32, [c_vp, c_i32, P(UPutSegmentInfo)]),
     "ghx_epochs_create": (c_i32, [ctypes.c_char_p, c_i32, c_i32, c_i32, ctypes.c_double, P(c_vp)]),
     "ghx_epochs_unlink": (c_i32, [ctypes.c_char_p]),
     "ghx_epochs_peers": (c_i32, [c_vp, P(c_i32), c_i32, P(c_i32), c_i32]),

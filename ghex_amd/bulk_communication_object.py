@@ -9,6 +9,10 @@ target side address the same message positions, so a lane moves element p regist
 the same copy inside one field. Cubed-sphere fields take the object in its cubed-sphere mode
 (structured.cubed_sphere.make_bulk_communication_object): its plans come from ghx_cs_put_create,
 whose launch (k_put_cs) also rotates and sign-flips the halos that cross a cube edge.
+Unstructured fields (unstructured.DataDescriptor) go into the plain object, alone or next to
+structured ones: their messages are index lists, planned by ghx_uput_create (the sender's send
+list and the receiver's receive list of the same key; k_put_u reads both index tables and moves
+each value field to field). A put plan holds messages of one kind.
 
 Usage mirrors the reference:
     bco = make_bulk_communication_object(ctx)
@@ -142,15 +146,25 @@ def field_records(bis, groups, export=True):
     its receive halos as (remote id, tag, spaces). A plain field's spaces are (local first, local
     last); a cubed-sphere field's record also carries its CsItem bytes ("cs") and each of its
     spaces the global box and its tile: (local first, local last, global first, global last,
-    tile) — what ghx_cs_put_create needs of the receiving side."""
+    tile) — what ghx_cs_put_create needs of the receiving side. An unstructured field's record
+    has "kind": 1, its UDataDesc bytes as "desc" and, as the spaces of each halo, the receive list
+    as one int64 NumPy array (all ranks' lists travel through the all-gather: no Python lists)."""
     out = []
     for bi, (d, j) in zip(bis, groups):
         rec = {"domain": d, "j": j, "desc": bytes(bi.field.desc)}
+        kind = getattr(bi.field, "kind", 0)
+        if kind:
+            rec["kind"] = kind
         if export:
             h = (ctypes.c_ubyte * 64)()
             off = ctypes.c_uint64()
             _ghx.call("ghx_ipc_export", ctypes.c_void_p(bi.field.data_ptr()), h, ctypes.byref(off))
             rec["ipc"], rec["offset"] = bytes(h), off.value
+        if kind == 1:
+            rec["recv"] = [(rid, tag, lids) for rid, rr, tag, lids in
+                           bi.pattern_container.lid_arrays(bi.local_index, 1)]
+            out.append(rec)
+            continue
         halos = bi.pattern_container.recv_halos(bi.local_index)
         cs = getattr(bi.field, "cs_item", None)
         if cs is None:
@@ -198,14 +212,19 @@ def put_messages(bis, groups, allr, local):
     field) paired with the receive halo of (my domain d, tag) on the target rank's j-th field of
     the receiving domain (the reference's put ranges, bulk_communication_object.hpp:384-455).
     bis[k] needs .pattern_container / .local_index; allr[r] = rank r's gathered setup record;
-    groups = _field_groups(); local = the ranks on this host."""
+    groups = _field_groups(); local = the ranks on this host. The spaces of a structured
+    message are lists of (local first, local last) boxes, those of an unstructured message one
+    int64 NumPy array of local indices per side (message_kind tells them apart)."""
     target = {}
     for r, info in enumerate(allr):
         for i, f in enumerate(info["fields"]):
             target[(r, f["domain"], f["j"])] = (r, i)
     msgs = []
     for k, (bi, (d, j)) in enumerate(zip(bis, groups)):
-        for rid, rr, tag, spaces in bi.pattern_container.send_halos(bi.local_index):
+        kind = 1 if bi.pattern_container.kind == "unstructured" else 0
+        halos = (bi.pattern_container.lid_arrays(bi.local_index, 0) if kind == 1 else
+                 bi.pattern_container.send_halos(bi.local_index))
+        for rid, rr, tag, spaces in halos:
             if rr not in local:
                 continue  # a remote rank: the buffered exchange carries it
             key = (rr, rid, j)
@@ -213,19 +232,32 @@ def put_messages(bis, groups, allr, local):
                 raise RuntimeError(f"rank {rr} registered no field #{j} for domain {rid}")
             tr, ti = target[key]
             tf = allr[tr]["fields"][ti]
+            if tf.get("kind", 0) != kind:
+                raise RuntimeError(f"field #{j} of domain {rid} on rank {rr} is not of the kind "
+                                   f"of its source field")
             tsp = next((sp for (sid, stag, sp) in tf["recv"] if sid == d and stag == tag), None)
             if tsp is None:
                 raise RuntimeError(f"no receive halo on rank {tr} for domain {d}, tag {tag}")
-            msgs.append((k, [(sp[0], sp[1]) for sp in spaces], (tr, ti), tsp))
+            msgs.append((k, spaces if kind == 1 else [(sp[0], sp[1]) for sp in spaces],
+                         (tr, ti), tsp))
     return msgs
+
+
+def message_kind(m) -> int:
+    """0: a structured message of put_messages (spaces are lists of boxes), 1: an unstructured
+    one (each side's spaces are one NumPy array of local indices)."""
+    return 0 if isinstance(m[1], (list, tuple)) else 1
 
 
 def put_chunks(msgs):
     """Messages grouped into put plans (one launch each) of <= 64 messages, <= 64 source and
-    <= 64 target fields: [(chunk, source field indices, target (rank, index) list)]."""
+    <= 64 target fields, all of one kind (a chunk ends where structured messages follow
+    unstructured ones or the reverse): [(chunk, source field indices, target (rank, index)
+    list)]."""
     out, chunk, srcs, dsts = [], [], [], []
     for m in msgs + [None]:
         if (m is None or len(chunk) == MAX_SLOTS or
+                (chunk and message_kind(m) != message_kind(chunk[0])) or
                 (m[0] not in srcs and len(srcs) == MAX_SLOTS) or
                 (m[2] not in dsts and len(dsts) == MAX_SLOTS)):
             if chunk:
@@ -265,6 +297,28 @@ def put_entries(chunk, srcs, dsts, src_descs, allr):
             e.buffer_offset = 0
             e.boxes = ctypes.cast(arr, ctypes.POINTER(_ghx.Box))
             e.n_boxes = len(spaces)
+    return src, dst, keep
+
+
+def uput_entries(chunk, srcs, dsts, src_descs, allr):
+    """ghx_uput_create's two entry arrays for one chunk of unstructured messages: entry b of
+    each is message b; the source side names this rank's fields (src_descs[k]), the target side
+    the target ranks' data descriptors as gathered. Returns (src, dst, keep-alive list)."""
+    import numpy as np
+    n = len(chunk)
+    src = (_ghx.UPutEntry * max(1, n))()
+    dst = (_ghx.UPutEntry * max(1, n))()
+    keep = [src, dst]
+    for b, (k, sl, tgt, tl) in enumerate(chunk):
+        tdesc = _ghx.UDataDesc.from_buffer_copy(allr[tgt[0]]["fields"][tgt[1]]["desc"])
+        for e, desc, slot, lids in ((src[b], src_descs[k], srcs.index(k), sl),
+                                    (dst[b], tdesc, dsts.index(tgt), tl)):
+            arr = np.ascontiguousarray(lids, dtype=np.int64)
+            keep.append(arr)
+            e.data = desc
+            e.field_slot = slot
+            e.lids = _ghx.i64_ptr(arr)
+            e.n_lids = arr.size
     return src, dst, keep
 
 
@@ -330,8 +384,14 @@ class BulkCommunicationObject:
     def add_field(self, bi):
         if self._initialized:
             raise RuntimeError("error: this bulk communication object has been initialized already")
-        if bi.field.kind != 0:
-            raise TypeError("bulk (zero-copy) exchange is implemented for structured fields")
+        if bi.field.kind not in (0, 1):
+            raise TypeError("bulk (zero-copy) exchange is implemented for structured and "
+                            "unstructured fields")
+        if bi.field.kind == 1:
+            if self.cubed_sphere:
+                raise ValueError("a cubed-sphere bulk exchange takes cubed-sphere fields only")
+            self._bis.append(bi)
+            return
         is_cs = getattr(bi.field, "cs_item", None) is not None
         if is_cs and not self.cubed_sphere:
             # a plain put copies field to field in the sender's orientation: it cannot rotate a
@@ -412,14 +472,19 @@ class BulkCommunicationObject:
         self._initialized = True
 
     def _make_put(self, chunk, srcs, dsts, allr, ptr_of):
-        src, dst, keep = put_entries(chunk, srcs, dsts, [bi.field.desc for bi in self._bis], allr)
+        descs = [bi.field.desc for bi in self._bis]
         n = len(chunk)
         h = ctypes.c_void_p()
-        if self.cubed_sphere:
+        if message_kind(chunk[0]) == 1:
+            src, dst, keep = uput_entries(chunk, srcs, dsts, descs, allr)
+            _ghx.call("ghx_uput_create", src, dst, n, ctypes.byref(h))
+        elif self.cubed_sphere:
+            src, dst, keep = put_entries(chunk, srcs, dsts, descs, allr)
             items, gptr, tptr, more = cs_put_args(chunk, allr)
             _ghx.call("ghx_cs_put_create", src, n, dst, n, items, gptr, tptr, ctypes.byref(h))
             keep = keep + more
         else:
+            src, dst, keep = put_entries(chunk, srcs, dsts, descs, allr)
             _ghx.call("ghx_put_create", src, n, dst, n, ctypes.byref(h))
         sp = _ghx.ptr_array([self._bis[k].field.data_ptr() for k in srcs])
         dp = _ghx.ptr_array([ptr_of[t] for t in dsts])
@@ -498,6 +563,8 @@ def make_bulk_communication_object(context, epochs: str = "device", timeout: flo
     """epochs="device": stream-ordered per-pair epochs (no host synchronisation); "host": the
     drain + barrier form. timeout: seconds an epoch wait may take before wait() raises.
     remote_options: CommunicationObject options for the halos of ranks on other hosts (e.g.
-    staging="host"); node-local ranks always get puts."""
+    staging="host"); node-local ranks always get puts. Takes structured fields and unstructured
+    ones (unstructured.DataDescriptor), also together; cubed-sphere fields have their own
+    structured.cubed_sphere.make_bulk_communication_object."""
     return BulkCommunicationObject(context, epochs=epochs, timeout=timeout,
                                    remote_options=remote_options)

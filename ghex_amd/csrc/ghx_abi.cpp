@@ -994,12 +994,65 @@ int ghx_cs_put_create(const ghx_pack_entry* src, int32_t n_src, const ghx_pack_e
     });
 }
 
+int ghx_uput_create(const ghx_uput_entry* src, const ghx_uput_entry* dst, int32_t n, ghx_put** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        *out = nullptr;
+        if (n < 0 || (n && (!src || !dst))) throw invalid("bad entry arrays");
+        *out = new ghx_put(std::make_unique<uput_plan>(src, dst, n));
+        return GHX_OK;
+    });
+}
+
+int ghx_uput_segment(const ghx_put* put, int32_t k, ghx_uput_segment_info* out)
+{
+    return guarded([&] {
+        check_ptr(put, "put");
+        check_ptr(out, "out");
+        const uput_plan* p = put->u.get();
+        if (!p) throw invalid("not a put of ghx_uput_create");
+        if (k < 0 || size_t(k) >= p->segs.size()) throw invalid("segment index out of range");
+        const seg_up& s = p->segs[size_t(k)];
+        *out = ghx_uput_segment_info{};
+        out->src_field_off = s.src_field_off;
+        out->src_index_stride_b = s.src_index_stride_b;
+        out->src_level_stride_b = s.src_level_stride_b;
+        out->dst_field_off = s.dst_field_off;
+        out->dst_index_stride_b = s.dst_index_stride_b;
+        out->dst_level_stride_b = s.dst_level_stride_b;
+        out->first_index = p->first[size_t(k)];
+        out->bytes = s.bytes;
+        out->row_bytes = s.row_bytes;
+        out->tile_bytes = s.tile_bytes;
+        out->n = s.n;
+        out->message = p->message[size_t(k)];
+        out->n_segments = int32_t(p->segs.size());
+        out->src_slot = s.src_slot;
+        out->dst_slot = s.dst_slot;
+        out->mode = s.mode;
+        out->wlog2 = s.wlog2;
+        out->src_lid64 = s.src_lid64;
+        out->dst_lid64 = s.dst_lid64;
+        out->src_runs = s.src_runs;
+        out->dst_runs = s.dst_runs;
+        return GHX_OK;
+    });
+}
+
 int ghx_cs_put_info(const ghx_put* put, int32_t* n_pair_tiles, int32_t* n_x_records,
                     int32_t* n_x_tiles)
 {
     return guarded([&] {
         check_ptr(put, "put");
         const cs_put_plan* p = put->cs.get();
+        if (put->u)
+        {
+            if (n_pair_tiles) *n_pair_tiles = int32_t(put->u->recs.size());
+            if (n_x_records) *n_x_records = 0;
+            if (n_x_tiles) *n_x_tiles = 0;
+            return GHX_OK;
+        }
         if (n_pair_tiles) *n_pair_tiles = p ? int32_t(p->n_pair_tiles()) : int32_t(put->from->first().n_tiles);
         if (n_x_records) *n_x_records = p ? p->n_x_records : 0;
         if (n_x_tiles) *n_x_tiles = p ? int32_t(p->n_x_tiles()) : 0;
@@ -1012,7 +1065,7 @@ int ghx_put_execute(const ghx_put* put, void* const* src_fields, int32_t n_src,
 {
     return guarded([&] {
         check_ptr(put, "put");
-        if (put->cs)
+        if (put->cs || put->u)
         {
             check_ptr(src_fields, "src_fields");
             check_ptr(dst_fields, "dst_fields");
@@ -1029,6 +1082,12 @@ int ghx_put_info(const ghx_put* put, uint64_t* bytes, int32_t* n_tiles)
         {
             if (bytes) *bytes = put->cs->bytes;
             if (n_tiles) *n_tiles = int32_t(put->cs->n_pair_tiles() + put->cs->n_x_tiles());
+            return GHX_OK;
+        }
+        if (put->u)
+        {
+            if (bytes) *bytes = put->u->bytes;
+            if (n_tiles) *n_tiles = int32_t(put->u->recs.size());
             return GHX_OK;
         }
         if (bytes) *bytes = put->from->bytes;

@@ -695,9 +695,12 @@ ghx_put::ghx_put(const ghx_pack_entry* src, int n_src, const ghx_pack_entry* dst
 
 ghx_put::ghx_put(std::unique_ptr<ghx::cs_put_plan> p) : cs(std::move(p)) {}
 
+ghx_put::ghx_put(std::unique_ptr<ghx::uput_plan> p) : u(std::move(p)) {}
+
 int ghx_put::execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const
 {
     if (cs) return cs->execute(src, ns, dst, nd, stream);
+    if (u) return u->execute(src, ns, dst, nd, stream);
     const ghx::splan& p = *from;
     const ghx::splan& q = *to;
     if (p.first().n_tiles == 0) return GHX_OK;

@@ -125,8 +125,11 @@ struct ghx_put
     ghx::device_tables recs;  // pair records (source segment with tile index, target segment)
     // a put made by ghx_cs_put_create: `cs` alone (pair records and put tile records, k_put_cs)
     std::unique_ptr<ghx::cs_put_plan> cs;
+    // a put made by ghx_uput_create: `u` alone (index-list tile records, k_put_u)
+    std::unique_ptr<ghx::uput_plan> u;
     ghx_put(const ghx_pack_entry* src, int n_src, const ghx_pack_entry* dst, int n_dst);
     explicit ghx_put(std::unique_ptr<ghx::cs_put_plan> p);
+    explicit ghx_put(std::unique_ptr<ghx::uput_plan> p);
     int execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const;
 };
 

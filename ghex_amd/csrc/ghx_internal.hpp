@@ -154,6 +154,37 @@ struct alignas(16) seg_u
 };
 static_assert(sizeof(seg_u) == 96, "seg_u layout");
 
+// Index-list put segment (k_put_u): the send list of a message on the sending
+// field and the receive list of the same message on the receiving field, with ONE row
+// decomposition of the message bytes for both sides (mode, row_bytes, mag_*: as seg_u's). Message
+// row r = (i, l) by `mode` sits at field_off + lid[i] * index_stride_b + l * level_stride_b of
+// its side. A put has no buffer; its tile records are this record with the tile's index in
+// first_tile, one per workgroup.
+struct alignas(16) seg_up
+{
+    const void* src_lids;      // device arrays, int32 or int64 per side
+    const void* dst_lids;
+    int64_t src_index_stride_b, src_level_stride_b, src_field_off;
+    int64_t dst_index_stride_b, dst_level_stride_b, dst_field_off;
+    magic_u32 mag_row;         // division by row_bytes
+    magic_u32 mag_inner;       // mode 1: by the levels; mode 2: by n
+    uint32_t n;                // number of indices
+    uint32_t row_levels;       // mode 1: the levels
+    uint32_t row_bytes;
+    uint32_t bytes;
+    uint32_t first_tile;
+    uint32_t tile_bytes;
+    uint16_t src_slot, dst_slot;
+    uint8_t wlog2;             // widest vector dividing the row and both sides' offsets and strides
+    uint8_t mode;              // as seg_u::mode, common to both sides
+    uint8_t src_lid64, dst_lid64;
+    uint8_t src_runs, dst_runs;  // the side's rows of consecutive lids are adjacent (4/8-B rows,
+                                 // mode 0, index stride = row): it may move a 16-B chunk in one
+                                 // access (put_runs); 2: at least half of its chunks are runs
+    uint8_t pad[14];
+};
+static_assert(sizeof(seg_up) == 128, "seg_up layout");
+
 // Transformed segment (cubed sphere): an iteration space received from another
 // cube tile whose rotation moves or reverses the field's stride-1 axis, or negates a vector
 // component (cubed_sphere/field_descriptor.hpp:81-108). The buffer holds the dense box in the
@@ -300,6 +331,8 @@ int launch_put(const kargs& a, void* stream, uint32_t grid);
 int launch_unpack_x(const kargs& a, void* stream, uint32_t grid);  // tile_recs: seg_x records
 int launch_self_cs(const kargs_cs& a, void* stream, uint32_t grid);
 int launch_put_cs(const kargs_pcs& a, void* stream, uint32_t grid);
+// tile_recs: seg_up records; field_ptr / buf_ptr: the source / target fields (as launch_put)
+int launch_put_u(const kargs& a, void* stream, uint32_t grid, bool runs);
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

@@ -1108,6 +1108,282 @@ __global__ __launch_bounds__(kBlock) void k_put_cs(kargs_pcs a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Index-list put (seg_up): send list on the sending field -> receive list on the receiving field.
+// ---------------------------------------------------------------------------------------------
+
+// kU lids of one table at idx[], all loads issued together (WIDE: int64 entries)
+template<bool WIDE>
+__device__ __forceinline__ void gather_lids(const void* table, const uint32_t (&idx)[kU], int64_t (&lid)[kU])
+{
+#pragma unroll
+    for (int u = 0; u < kU; ++u)
+    {
+        if constexpr (WIDE) lid[u] = ((const GHX_GLOBAL int64_t*)(table))[idx[u]];
+        else lid[u] = ((const GHX_GLOBAL int32_t*)(table))[idx[u]];
+    }
+}
+
+// General path, the shape of copy_tile_u: per loop trip a lane takes kU message positions (one past
+// the tile's end is clamped to the tile's last vector and moves the same bytes to the same
+// address again), decodes each once into (index, level, remainder) by the common mode, then
+// issues all kU index loads of the source table and all kU of the target table, all kU value
+// loads from the source field, all kU stores to the target field. The uniform choices (table
+// widths S64 / D64, vector width W: template arguments; the mode: one branch around the whole
+// decode) stay out of the per-vector code, so no load waits for the one before it.
+template<int W, bool S64, bool D64>
+__device__ __forceinline__ void put_tile_u(const seg_up& s, const char* __restrict__ src,
+                                           char* __restrict__ dst, uint32_t start, uint32_t end)
+{
+    using V = typename vec_t<W>::type;
+    const uint32_t last = end - W;  // tiles hold whole rows: end - start is a multiple of W
+    src += s.src_field_off;
+    dst += s.dst_field_off;
+    for (uint32_t base = start + threadIdx.x * W; base < end; base += kU * kBlock * W)
+    {
+        uint32_t idx[kU], lev[kU], rem[kU];
+        if (s.mode == 0)
+        {
+#pragma unroll
+            for (int u = 0; u < kU; ++u)
+            {
+                const uint32_t p = min(base + uint32_t(u) * kBlock * W, last);
+                idx[u] = fastdiv(p, s.mag_row);
+                lev[u] = 0;
+                rem[u] = p - idx[u] * s.row_bytes;
+            }
+        }
+        else if (s.mode == 1)
+        {
+#pragma unroll
+            for (int u = 0; u < kU; ++u)
+            {
+                const uint32_t p = min(base + uint32_t(u) * kBlock * W, last);
+                const uint32_t row = fastdiv(p, s.mag_row);
+                idx[u] = fastdiv(row, s.mag_inner);
+                lev[u] = row - idx[u] * s.row_levels;
+                rem[u] = p - row * s.row_bytes;
+            }
+        }
+        else
+        {
+#pragma unroll
+            for (int u = 0; u < kU; ++u)
+            {
+                const uint32_t p = min(base + uint32_t(u) * kBlock * W, last);
+                const uint32_t row = fastdiv(p, s.mag_row);
+                lev[u] = fastdiv(row, s.mag_inner);
+                idx[u] = row - lev[u] * s.n;
+                rem[u] = p - row * s.row_bytes;
+            }
+        }
+        int64_t sl[kU], dl[kU];
+        gather_lids<S64>(s.src_lids, idx, sl);
+        gather_lids<D64>(s.dst_lids, idx, dl);
+        V v[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+            v[u] = vload<V>(src + sl[u] * s.src_index_stride_b + int64_t(lev[u]) * s.src_level_stride_b + rem[u]);
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+            vstore<V>(dst + dl[u] * s.dst_index_stride_b + int64_t(lev[u]) * s.dst_level_stride_b + rem[u], v[u]);
+    }
+}
+
+template<bool S64, bool D64>
+__device__ __forceinline__ void put_tile_u_w(const seg_up& s, const char* src, char* dst,
+                                             uint32_t start, uint32_t end, int w)
+{
+    switch (w)
+    {
+        case 4: put_tile_u<16, S64, D64>(s, src, dst, start, end); break;
+        case 3: put_tile_u<8, S64, D64>(s, src, dst, start, end); break;
+        case 2: put_tile_u<4, S64, D64>(s, src, dst, start, end); break;
+        case 1: put_tile_u<2, S64, D64>(s, src, dst, start, end); break;
+        default: put_tile_u<1, S64, D64>(s, src, dst, start, end); break;
+    }
+}
+
+// K consecutive lids of one table from position r0 with one vector load per 16 B (r0 a multiple
+// of K: the table and the tile start are 16-B aligned, a lane's chunk K rows)
+template<int K>
+__device__ __forceinline__ void load_lid_chunk(const void* table, bool wide, uint32_t r0, int64_t (&l)[K])
+{
+    if (wide)
+    {
+        const GHX_GLOBAL vec_t<16>::type* p = (const GHX_GLOBAL vec_t<16>::type*)((const int64_t*)(table) + r0);
+#pragma unroll
+        for (int j = 0; j < K; j += 2)
+        {
+            const auto q = p[j / 2];
+            l[j] = int64_t(uint64_t(q.x) | (uint64_t(q.y) << 32));
+            l[j + 1] = int64_t(uint64_t(q.z) | (uint64_t(q.w) << 32));
+        }
+    }
+    else if constexpr (K == 2)
+    {
+        const auto q = *(const GHX_GLOBAL vec_t<8>::type*)((const int32_t*)(table) + r0);
+        l[0] = int32_t(q.x);
+        l[1] = int32_t(q.y);
+    }
+    else
+    {
+        const auto q = *(const GHX_GLOBAL vec_t<16>::type*)((const int32_t*)(table) + r0);
+        l[0] = int32_t(q.x);
+        l[1] = int32_t(q.y);
+        l[2] = int32_t(q.z);
+        l[3] = int32_t(q.w);
+    }
+}
+
+__device__ __forceinline__ int64_t load_lid_one(const void* table, bool wide, uint32_t i)
+{
+    if (wide) return ((const GHX_GLOBAL int64_t*)(table))[i];
+    return ((const GHX_GLOBAL int32_t*)(table))[i];
+}
+
+// Run path, the shape of copy_runs: rows of L = 4 or 8 bytes (mode 0), a lane owns K = 16 / L
+// consecutive message rows and loads its K lids of each table with one vector load. A side whose
+// K lids form a run (lid[j] = lid[0] + j) and whose rows of consecutive lids are adjacent in its
+// field (seg_up::src_runs / dst_runs: its index stride is L) moves the 16 bytes in ONE access,
+// else row by row; the two sides decide independently, so a wave may hold all four combinations
+// (masked). A side that never forms runs still takes its offsets from its own index stride. A
+// segment tail of fewer than K rows goes row by row; no lid is read at or beyond n.
+template<int L>
+__device__ __forceinline__ void put_runs(const seg_up& s, const char* __restrict__ src,
+                                         char* __restrict__ dst, uint32_t start, uint32_t end)
+{
+    using V = typename vec_t<16>::type;
+    using R = typename vec_t<L>::type;
+    constexpr int K = 16 / L;
+    src += s.src_field_off;
+    dst += s.dst_field_off;
+    for (uint32_t base = start + threadIdx.x * 16; base < end; base += kU * kBlock * 16)
+    {
+        int64_t so[kU][K], to[kU][K];
+        uint32_t full = 0, srun = 0, drun = 0;  // bit u: chunk u holds K rows / its side is a run
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+        {
+            const uint32_t p = base + u * kBlock * 16;
+            if (p >= end) continue;
+            const uint32_t r0 = p / L;
+            int64_t ls[K], ld[K];
+            if (p + 16 <= end)
+            {
+                full |= 1u << u;
+                load_lid_chunk<K>(s.src_lids, s.src_lid64, r0, ls);
+                load_lid_chunk<K>(s.dst_lids, s.dst_lid64, r0, ld);
+                bool cs = s.src_runs != 0, cd = s.dst_runs != 0;
+#pragma unroll
+                for (int j = 1; j < K; ++j)
+                {
+                    cs = cs && ls[j] == ls[0] + j;
+                    cd = cd && ld[j] == ld[0] + j;
+                }
+                if (cs) srun |= 1u << u;
+                if (cd) drun |= 1u << u;
+            }
+            else
+            {
+#pragma unroll
+                for (int j = 0; j < K; ++j)
+                {
+                    const bool in = p + j * L < end;
+                    ls[j] = in ? load_lid_one(s.src_lids, s.src_lid64, r0 + j) : 0;
+                    ld[j] = in ? load_lid_one(s.dst_lids, s.dst_lid64, r0 + j) : 0;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+            {
+                so[u][j] = ls[j] * s.src_index_stride_b;
+                to[u][j] = ld[j] * s.dst_index_stride_b;
+            }
+        }
+        V v[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+        {
+            if (!(full >> u & 1u)) continue;
+            if (srun >> u & 1u)
+            {
+                const v4_a4 x = vload<v4_a4>(src + so[u][0]);
+                v[u] = V{x.x, x.y, x.z, x.w};
+            }
+            else
+            {
+                R w[K];
+#pragma unroll
+                for (int j = 0; j < K; ++j) w[j] = vload<R>(src + so[u][j]);
+                v[u] = assemble<L>(w);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+        {
+            const uint32_t p = base + u * kBlock * 16;
+            if (p >= end) continue;
+            if (!(full >> u & 1u))
+            {
+                // segment tail: fewer than K rows left, row by row
+#pragma unroll
+                for (int j = 0; j < K; ++j)
+                {
+                    if (p + j * L >= end) break;
+                    vstore<R>(dst + to[u][j], vload<R>(src + so[u][j]));
+                }
+                continue;
+            }
+            if (drun >> u & 1u)
+                vstore<v4_a4>(dst + to[u][0], v4_a4{v[u].x, v[u].y, v[u].z, v[u].w});
+            else
+            {
+                R w[K];
+                split<L>(v[u], w);
+#pragma unroll
+                for (int j = 0; j < K; ++j) vstore<R>(dst + to[u][j], w[j]);
+            }
+        }
+    }
+}
+
+// One tile record per workgroup at its block index (grid-stride beyond the grid cap). RUNS: every
+// segment of the plan takes the run path (uput_plan::execute decides with the launch's pointers),
+// so neither path's registers weigh on the other. Source field slot s at field_ptr[s], target
+// field slot d at buf_ptr[d], as k_put's.
+template<bool RUNS>
+__global__ __launch_bounds__(kBlock) void k_put_u(kargs a)
+{
+    const seg_up* __restrict__ recs = static_cast<const seg_up*>(a.tile_recs);
+    for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x)
+    {
+        const seg_up s = recs[t];
+        const uint32_t start = s.first_tile * s.tile_bytes;
+        const uint32_t end = min(start + s.tile_bytes, s.bytes);
+        const char* src = reinterpret_cast<const char*>(a.field_ptr[s.src_slot]);
+        char* dst = reinterpret_cast<char*>(a.buf_ptr[s.dst_slot]);
+        if constexpr (RUNS)
+        {
+            if (s.row_bytes == 8) put_runs<8>(s, src, dst, start, end);
+            else put_runs<4>(s, src, dst, start, end);
+        }
+        else
+        {
+            int w = s.wlog2;
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(src)));
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(dst)));
+            if (s.src_lid64)
+            {
+                if (s.dst_lid64) put_tile_u_w<true, true>(s, src, dst, start, end, w);
+                else put_tile_u_w<true, false>(s, src, dst, start, end, w);
+            }
+            else if (s.dst_lid64) put_tile_u_w<false, true>(s, src, dst, start, end, w);
+            else put_tile_u_w<false, false>(s, src, dst, start, end, w);
+        }
+    }
+}
+
 int launched(const char* what)
 {
     const hipError_t e = hipGetLastError();
@@ -1235,6 +1511,15 @@ int launch_put_cs(const kargs_pcs& a, void* stream, uint32_t grid)
     if (n_tiles == 0) return GHX_OK;
     launch(k_put_cs, min(grid, n_tiles), static_cast<hipStream_t>(stream), a);
     return launched("cubed-sphere put");
+}
+
+int launch_put_u(const kargs& a, void* stream, uint32_t grid, bool runs)
+{
+    if (a.n_tiles == 0) return GHX_OK;
+    grid = min(grid, a.n_tiles);
+    if (runs) launch(k_put_u<true>, grid, static_cast<hipStream_t>(stream), a);
+    else launch(k_put_u<false>, grid, static_cast<hipStream_t>(stream), a);
+    return launched("index-list put");
 }
 
 template<bool DBL, bool REC>

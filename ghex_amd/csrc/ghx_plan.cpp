@@ -1117,4 +1117,232 @@ int uplan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* s
     });
 }
 
+// ---------------------------------------------------------------------------------------------
+// index-list put
+// ---------------------------------------------------------------------------------------------
+uput_plan::uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n_entries)
+{
+    auto mag = [](int64_t v) { return uint64_t(v < 0 ? -v : v); };
+    // both sides' index lists in one device allocation: int32 where a list fits, per list
+    struct lid_upload
+    {
+        const int64_t* lids;
+        int64_t n;
+        bool wide;
+        size_t off;
+    };
+    std::vector<lid_upload> uploads;
+    std::map<std::pair<const int64_t*, int64_t>, size_t> lid_off;  // -> index into uploads
+    std::vector<std::pair<size_t, size_t>> pend;                   // per segment: src / dst upload
+    size_t lid_bytes = 0;
+    auto wide_list = [](const ghx_uput_entry& en) {
+        bool wide = false;
+        for (int64_t i = 0; i < en.n_lids; ++i)
+        {
+            if (en.lids[i] < 0) throw invalid("negative local index");
+            if (en.lids[i] >= (int64_t(1) << 31)) wide = true;
+        }
+        return wide;
+    };
+    auto table = [&](const int64_t* lids, int64_t n, bool wide) {
+        const auto key = std::make_pair(lids, n);
+        auto it = lid_off.find(key);
+        if (it != lid_off.end() && uploads[it->second].wide == wide) return it->second;
+        lid_bytes = (lid_bytes + 15) & ~size_t(15);
+        uploads.push_back({lids, n, wide, lid_bytes});
+        lid_bytes += size_t(n) * (wide ? 8 : 4);
+        lid_off[key] = uploads.size() - 1;
+        return uploads.size() - 1;
+    };
+    // at least half of the list's 16-B chunks hold 16/L consecutive lids
+    auto run_heavy = [](const int64_t* li, int64_t n, int64_t L) {
+        const int64_t K = 16 / L, chunks = n / K;
+        int64_t hits = 0;
+        for (int64_t c = 0; c < chunks; ++c)
+        {
+            bool run = true;
+            for (int64_t j = 1; j < K && run; ++j) run = li[c * K + j] == li[c * K] + j;
+            hits += run ? 1 : 0;
+        }
+        return chunks > 0 && 2 * hits >= chunks;
+    };
+    for (int e = 0; e < n_entries; ++e)
+    {
+        const ghx_uput_entry &se = src[e], &de = dst[e];
+        const ghx_udata_desc &sd = se.data, &dd = de.data;
+        if (sd.elem_size < 1 || sd.levels < 1 || dd.elem_size < 1 || dd.levels < 1)
+            throw invalid("bad unstructured data descriptor");
+        if (se.field_slot < 0 || de.field_slot < 0) throw invalid("negative slot");
+        if (se.field_slot >= GHX_MAX_SLOTS || de.field_slot >= GHX_MAX_SLOTS)
+            throw invalid("a put plan takes at most 64 source and 64 target fields (one launch)");
+        if (se.n_lids < 0 || de.n_lids < 0 || (se.n_lids > 0 && !se.lids) || (de.n_lids > 0 && !de.lids))
+            throw invalid("bad index list");
+        if (se.n_lids != de.n_lids || sd.elem_size != dd.elem_size || sd.levels != dd.levels ||
+            (sd.levels_first != 0) != (dd.levels_first != 0))
+            throw invalid("source and target index lists do not describe the same message bytes "
+                          "(list lengths, element sizes, levels or level order differ)");
+        max_src_slot = std::max(max_src_slot, se.field_slot);
+        max_dst_slot = std::max(max_dst_slot, de.field_slot);
+        const bool swide = wide_list(se), dwide = wide_list(de);
+        const int64_t elem = sd.elem_size;
+        const int64_t per_index = int64_t(sd.levels) * elem;
+        constexpr int64_t kSegLimit = int64_t(1) << 30;
+        if (per_index > kSegLimit) throw invalid("unstructured row of more than 1 GiB");
+        if (se.n_lids == 0) continue;
+        // uplan's rule for both sides together: whole-index rows only where the levels are
+        // contiguous on both
+        const bool contiguous = sd.levels == 1 ||
+                                (sd.levels_first && sd.level_stride == 1 && dd.level_stride == 1);
+        const int mode = contiguous ? 0 : sd.levels_first ? 1 : 2;
+        // one segment of index range [a, a + n) of both lists (mode 2 split: one level `lev`, as a
+        // mode-0 segment of elem-byte rows at each side's field offset lev * level stride)
+        auto add = [&](int64_t a, int64_t n, int m, int64_t lev) {
+            seg_up s{};
+            s.n = uint32_t(n);
+            s.src_index_stride_b = sd.index_stride * elem;
+            s.src_level_stride_b = sd.level_stride * elem;
+            s.dst_index_stride_b = dd.index_stride * elem;
+            s.dst_level_stride_b = dd.level_stride * elem;
+            s.src_field_off = lev >= 0 ? lev * s.src_level_stride_b : 0;
+            s.dst_field_off = lev >= 0 ? lev * s.dst_level_stride_b : 0;
+            s.src_lid64 = swide ? 1 : 0;
+            s.dst_lid64 = dwide ? 1 : 0;
+            s.src_slot = uint16_t(se.field_slot);
+            s.dst_slot = uint16_t(de.field_slot);
+            s.mode = uint8_t(m);
+            const int64_t Ls = m == 0 && lev < 0 ? per_index : elem;
+            if (m == 1)
+            {
+                s.row_levels = uint32_t(sd.levels);
+                s.mag_inner = make_magic(uint32_t(sd.levels));
+            }
+            else if (m == 2)
+                s.mag_inner = make_magic(uint32_t(n));
+            s.row_bytes = uint32_t(Ls);
+            s.bytes = uint32_t(n * (m == 0 ? Ls : per_index));
+            s.mag_row = make_magic(uint32_t(Ls));
+            int w = wlog2_of(uint64_t(Ls));
+            w = std::min(w, wlog2_of(mag(s.src_field_off)));
+            w = std::min(w, wlog2_of(mag(s.dst_field_off)));
+            if (n > 1)
+            {
+                w = std::min(w, wlog2_of(mag(s.src_index_stride_b)));
+                w = std::min(w, wlog2_of(mag(s.dst_index_stride_b)));
+            }
+            if (m != 0)
+            {
+                w = std::min(w, wlog2_of(mag(s.src_level_stride_b)));
+                w = std::min(w, wlog2_of(mag(s.dst_level_stride_b)));
+            }
+            s.wlog2 = uint8_t(w);
+            const bool chunked = g_tune.urun && m == 0 && (Ls == 4 || Ls == 8);
+            if (chunked && s.src_index_stride_b == Ls) s.src_runs = run_heavy(se.lids + a, n, Ls) ? 2 : 1;
+            if (chunked && s.dst_index_stride_b == Ls) s.dst_runs = run_heavy(de.lids + a, n, Ls) ? 2 : 1;
+            pend.emplace_back(table(se.lids + a, n, swide), table(de.lids + a, n, dwide));
+            segs.push_back(s);
+            message.push_back(e);
+            first.push_back(a);
+        };
+        const int64_t total = se.n_lids * per_index;
+        if (total <= kSegLimit && se.n_lids < (int64_t(1) << 32))
+            add(0, se.n_lids, mode, -1);
+        else if (mode != 2)
+        {
+            const int64_t step = kSegLimit / per_index;
+            for (int64_t a = 0; a < se.n_lids; a += step) add(a, std::min(step, se.n_lids - a), mode, -1);
+        }
+        else
+        {
+            const int64_t step = kSegLimit / elem;
+            for (int64_t lev = 0; lev < sd.levels; ++lev)
+                for (int64_t a = 0; a < se.n_lids; a += step) add(a, std::min(step, se.n_lids - a), 0, lev);
+        }
+        bytes += uint64_t(total);
+    }
+    // tiles by the index-list rule (build_tiles / short_tile_rows / long_tile_bytes of seg_u):
+    // whole rows; short rows by row count (run-heavy lists of either side: u_run_tile_rows)
+    run_ok = g_tune.urun != 0 && !segs.empty();
+    for (seg_up& s : segs)
+    {
+        uint32_t tb;
+        if (s.row_bytes < g_tune.small_row_bytes)
+        {
+            const uint32_t rows = s.src_runs == 2 || s.dst_runs == 2 ? g_tune.u_run_tile_rows : g_tune.u_tile_rows;
+            const uint64_t want = uint64_t(rows) * s.row_bytes;
+            tb = uint32_t(std::max<uint64_t>(s.row_bytes, std::min<uint64_t>(want, kMaxTileBytes)));
+        }
+        else
+            tb = std::max<uint32_t>(g_tune.u_tile_bytes, s.row_bytes);
+        s.tile_bytes = tb - tb % s.row_bytes;
+        run_ok = run_ok && s.mode == 0 && (s.row_bytes == 4 || s.row_bytes == 8) && s.tile_bytes % 16 == 0;
+    }
+    if (!segs.empty() && have_device())
+    {
+        std::vector<unsigned char> host(lid_bytes);
+        for (const lid_upload& p : uploads)
+        {
+            if (p.wide)
+            {
+                int64_t* to = reinterpret_cast<int64_t*>(host.data() + p.off);
+                for (int64_t i = 0; i < p.n; ++i) to[i] = p.lids[i];
+            }
+            else
+            {
+                int32_t* to = reinterpret_cast<int32_t*>(host.data() + p.off);
+                for (int64_t i = 0; i < p.n; ++i) to[i] = int32_t(p.lids[i]);
+            }
+        }
+        if (hipMalloc(&dev.lids, lid_bytes) != hipSuccess) throw hip_error("hipMalloc(put lids)");
+        if (hipMemcpy(dev.lids, host.data(), lid_bytes, hipMemcpyHostToDevice) != hipSuccess)
+            throw hip_error("hipMemcpy(put lids)");
+        for (size_t k = 0; k < segs.size(); ++k)
+        {
+            segs[k].src_lids = static_cast<char*>(dev.lids) + uploads[pend[k].first].off;
+            segs[k].dst_lids = static_cast<char*>(dev.lids) + uploads[pend[k].second].off;
+        }
+    }
+    // one record per tile; short-row segments first (g_tune.order, as build_tiles)
+    std::vector<size_t> idx(segs.size());
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
+    if (g_tune.order == 1)
+        std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) {
+            return (segs[a].row_bytes < g_tune.small_row_bytes) > (segs[b].row_bytes < g_tune.small_row_bytes);
+        });
+    for (size_t i : idx)
+    {
+        const uint32_t nt = tiles_of(segs[i].bytes, segs[i].tile_bytes);
+        for (uint32_t t = 0; t < nt; ++t)
+        {
+            recs.push_back(segs[i]);
+            recs.back().first_tile = t;
+        }
+    }
+    if (!recs.empty() && have_device())
+    {
+        const size_t rb = recs.size() * sizeof(seg_up);
+        if (hipMalloc(&dev.recs, rb) != hipSuccess) throw hip_error("hipMalloc(put tile records)");
+        if (hipMemcpy(dev.recs, recs.data(), rb, hipMemcpyHostToDevice) != hipSuccess)
+            throw hip_error("hipMemcpy(put tile records)");
+    }
+}
+
+int uput_plan::execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const
+{
+    if (recs.empty()) return GHX_OK;
+    if (!src || !dst || ns <= max_src_slot || nd <= max_dst_slot)
+        throw invalid("pointer arrays do not cover the plan's slots");
+    if (!dev.recs || !dev.lids) throw hip_error("plan has no device tables (no HIP device at creation)");
+    kargs a{};
+    a.tile_recs = dev.recs;
+    a.n_tiles = uint32_t(recs.size());
+    fill_slots(a.field_ptr, src, {}, max_src_slot + 1, "source field");
+    fill_slots(a.buf_ptr, dst, {}, max_dst_slot + 1, "target field");
+    // the run-path kernel when every segment qualifies with these pointers (both aligned to the row)
+    bool runs = run_ok;
+    for (size_t k = 0; runs && k < segs.size(); ++k)
+        runs = a.field_ptr[segs[k].src_slot] % segs[k].row_bytes == 0 &&
+               a.buf_ptr[segs[k].dst_slot] % segs[k].row_bytes == 0;
+    return launch_put_u(a, stream, grid_for_tiles(a.n_tiles), runs);
+}
+
 }  // namespace ghx

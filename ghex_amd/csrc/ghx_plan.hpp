@@ -216,6 +216,27 @@ struct uplan
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
 
+// Index-list put (k_put_u): message k's send list on the sending field and its
+// receive list on the receiving field, planned together: one row decomposition per message
+// (uplan's rule applied to both sides), tiles by the index-list rule, one tile record per
+// workgroup. Field slots: the sender's index the source pointer array, the receiver's the
+// target pointer array; fewer than GHX_MAX_SLOTS of each (one launch). Built without a device;
+// the records are kept on the host for inspection and uploaded when there is a device.
+struct uput_plan
+{
+    uint64_t bytes = 0;            // message bytes moved per execution
+    int max_src_slot = -1, max_dst_slot = -1;
+    std::vector<seg_up> segs;      // plan order, first_tile 0
+    std::vector<int32_t> message;  // per segment: its message, and
+    std::vector<int64_t> first;    // its first position in that message's lists
+    std::vector<seg_up> recs;      // one per tile, dispatch order
+    bool run_ok = false;           // every segment may take the run path (urun on, mode 0, rows
+                                   // of 4 or 8 B, tiles of whole 16-B chunks)
+    device_tables dev;             // recs: the tile records; lids: both sides' index lists
+    uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n);
+    int execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const;
+};
+
 // The per-call entry points' plans, cached by content (ghx_cache.cpp): the plan of the call's
 // descriptor and spaces, or index list, is built on first use and executed on `stream`.
 int run_structured(const ghx_field_desc& f, const ghx_box* boxes, int n, int dir, void* field,

@@ -679,6 +679,70 @@ int ghx_cs_put_create(const ghx_pack_entry* src, int32_t n_src, const ghx_pack_e
 int ghx_cs_put_info(const ghx_put* put, int32_t* n_pair_tiles, int32_t* n_x_records,
                     int32_t* n_x_tiles);
 
+/* A put plan over unstructured fields (no reference counterpart: the reference's bulk object is
+ * structured only). src[k] and dst[k] are the two ends of message k: a sender's send list on its
+ * field and the receiver's receive list for the same key on its field (ghx_pattern_key_lids of
+ * either side), n messages. Field slots: src entries index src_fields, dst entries dst_fields
+ * (< 64 each: one launch, no launch groups; the bulk object groups its messages into several put
+ * plans). Execution performs, for every i < n_lids and l < levels,
+ *   dst.values[(t[i]*dst.index_stride + l*dst.level_stride)*elem] <-
+ *   src.values[(s[i]*src.index_stride + l*src.level_stride)*elem]
+ * (s, t: the source and target lists), byte for byte what a ghx_uplan pack of the source side
+ * followed by a ghx_uplan unpack of the target side leaves in the target field — as ONE launch
+ * (k_put_u) with no buffer: both index tables are read together, each value is loaded from the
+ * source field and stored to the target field (this device's memory or a peer's through
+ * ghx_ipc_import). Messages of 4- or 8-byte rows move 16 bytes per lane, as one 16-byte access on
+ * a side whose lids form a run there (knob "urun"), as in the index-list pack. The result is an
+ * ordinary ghx_put for ghx_put_execute (stream-ordered, never allocates, capturable) /
+ * ghx_put_info (message bytes, workgroup tiles) / ghx_put_destroy; ghx_cs_put_info reports its
+ * tiles as pair tiles and zeros for the rest. Created without a device like every other plan
+ * (the tables are uploaded only when there is one; execution then reports GHX_ERR_HIP).
+ * GHX_ERR_INVALID, with the reason in ghx_last_error(), when: the two sides of a message differ
+ * in n_lids, elem_size, levels or levels_first (they would not describe the same message bytes:
+ * the buffered path pairs bytes by position); a lid is negative; elem_size < 1 or levels < 1; a
+ * slot is negative or >= 64; a row (levels * elem_size) is longer than 1 GiB.
+ * Contract, not checked: no source cell of an exchange is a target cell of the same exchange, and
+ * the target lids of one field are distinct (the patterns guarantee both: send lists hold inner
+ * cells, receive lists outer cells). Source lids may repeat. */
+typedef struct ghx_uput_entry
+{
+    ghx_udata_desc data;               /* this side's field */
+    int32_t field_slot;
+    const int64_t* lids;               /* HOST array (pattern order); copied to device memory as
+                                          int32, or int64 if any lid of the list is >= 2^31 */
+    int64_t n_lids;
+} ghx_uput_entry;
+int ghx_uput_create(const ghx_uput_entry* src, const ghx_uput_entry* dst, int32_t n, ghx_put** out);
+
+/* What the planner decided for segment k of a plan of ghx_uput_create (host only, the twin of
+ * ghx_uplan_segment): k in [0, n_segments), the messages in order, a message beyond 2^30 bytes as
+ * several segments (index ranges; a levels-last list level by level) cut identically on both
+ * sides. The segment covers positions [first_index, first_index + n) of both lists of message
+ * `message`. Message row r of the segment sits, on either side, at that side's
+ * field_off + lid[first_index + i] * index_stride_b + l * level_stride_b with (i, l) by the
+ * common `mode` as for ghx_usegment_info. row_bytes, bytes, tile_bytes (whole rows) and wlog2
+ * (the widest vector both sides allow; the launch narrows it by both pointers) are common;
+ * lid64 and runs are per side (runs: the side may form 16-byte runs; 2: run-heavy).
+ * GHX_ERR_INVALID for a put that did not come from ghx_uput_create, or k out of range. */
+typedef struct ghx_uput_segment_info
+{
+    int64_t src_field_off, src_index_stride_b, src_level_stride_b;
+    int64_t dst_field_off, dst_index_stride_b, dst_level_stride_b;
+    int64_t first_index;
+    uint32_t bytes;
+    uint32_t row_bytes;
+    uint32_t tile_bytes;
+    uint32_t n;
+    int32_t message;
+    int32_t n_segments;                /* of the whole plan */
+    int32_t src_slot, dst_slot;
+    int32_t mode;
+    int32_t wlog2;
+    int32_t src_lid64, dst_lid64;
+    int32_t src_runs, dst_runs;
+} ghx_uput_segment_info;
+int ghx_uput_segment(const ghx_put* put, int32_t k, ghx_uput_segment_info* out);
+
 /* Device-side access epochs of the zero-copy exchanges (bulk puts, direct pack): the reference's
  * access guards (include/ghex/rma/access_guard.hpp:35-140; per range: start/end_target_epoch on
  * the owner, start/end_source_epoch on the putter; include/ghex/bulk_communication_object.hpp
