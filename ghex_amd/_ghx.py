@@ -74,6 +74,10 @@ class UPutSegmentInfo(ctypes.Structure):
                 ("dst_runs", c_i32)]
 
 
+class USelfSegmentInfo(ctypes.Structure):
+    _fields_ = UPutSegmentInfo._fields_ + [("buf_slot", c_i32), ("buf_off", c_u64)]
+
+
 class RegularDomain(ctypes.Structure):
     _fields_ = [("id", c_i32), ("rank", c_i32), ("first", c_i32 * 3), ("last", c_i32 * 3)]
 
@@ -128,6 +132,13 @@ _SIGS = {
     "ghx_cs_plan_info": (c_i32, [c_vp, P(c_i32), P(c_u64), P(c_i32), P(c_i32)]),
     "ghx_cs_self_info": (c_i32, [c_vp, P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
     "ghx_cs_exchange_self": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_uself_create": (c_i32, [P(UPackEntry), P(UPackEntry), c_i32, P(c_vp)]),
+    "ghx_uself_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_uself_info": (c_i32, [c_vp, P(c_u64), P(c_i32), P(c_i32)]),
+    "ghx_uself_segment": (c_i32, [c_vp, c_i32, P(USelfSegmentInfo)]),
+    "ghx_uself_destroy": (c_i32, [c_vp]),
+    "ghx_uexchange_self_info": (c_i32, [c_vp, P(c_i32), P(c_i32), P(c_i32)]),
+    "ghx_uexchange_self": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
                               c_i32, c_vp]),
     "ghx_udomain_create": (c_i32, [c_i32, P(c_i64), c_i64, P(c_i64), c_i64, P(c_vp)]),

@@ -251,7 +251,8 @@ class CommunicationObject:
 
     def __init__(self, context, fuse_self: bool = True, staging=None, pipelined: bool = False,
                  rccl_self: bool = False, max_streams: int = 4, copy_engine: str = "probe",
-                 direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False):
+                 direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False,
+                 fuse_lists: bool = False):
         if staging not in (None, "host"):
             raise ValueError("staging must be None (device buffers) or 'host'")
         if direct and (staging is not None or pipelined or rccl_self):
@@ -275,6 +276,9 @@ class CommunicationObject:
         # cubed-sphere fields, every message on this rank: pack and rotating unpack in one launch
         # (ghx_cs_exchange_self). Opt-in; a plan that cannot be fused takes the usual path
         self.fuse_rotated = bool(fuse_rotated)
+        # unstructured fields, every message on this rank: pack and unpack in one launch
+        # (ghx_uexchange_self). Opt-in; a plan that cannot be fused takes the usual path
+        self.fuse_lists = bool(fuse_lists)
         self.staging = staging
         self.pipelined = pipelined
         # tests: route the self messages through RCCL too (a 1-rank communicator), so the
@@ -314,6 +318,15 @@ class CommunicationObject:
             _ghx.call("ghx_cs_self_info", plan.h, ctypes.byref(f), None, None, None)
             plan._cs_self = bool(f.value)
         return plan._cs_self
+
+    def lists_self(self, plan) -> bool:
+        """An exchange of unstructured fields whose every message is a self message and which
+        libghx has planned as one launch (ghx_uexchange_self_info, ghx_uexchange_self)."""
+        if getattr(plan, "_lists_self", None) is None:
+            f = ctypes.c_int32()
+            _ghx.call("ghx_uexchange_self_info", plan.h, ctypes.byref(f), None, None)
+            plan._lists_self = bool(f.value)
+        return plan._lists_self
 
     def mixed(self, plan) -> bool:
         """Self AND peer messages: the pack launch also completes the self messages
@@ -508,6 +521,13 @@ class CommunicationObject:
                                                  stream.cuda_stream)
             if rc:
                 _ghx.check(rc, "ghx_cs_exchange_self")
+            return CommunicationHandle(self, stream, self._done_event(stream))
+        if self.fuse_self and self.fuse_lists and self.lists_self(plan):
+            # index lists, every message on this rank: pack and unpack in one launch
+            rc = _ghx.lib().ghx_uexchange_self(plan.h, fptrs, len(bis), sptrs, len(send),
+                                               stream.cuda_stream)
+            if rc:
+                _ghx.check(rc, "ghx_uexchange_self")
             return CommunicationHandle(self, stream, self._done_event(stream))
         with torch.cuda.stream(stream):
             mixed = self.fuse_self and self.mixed(plan)

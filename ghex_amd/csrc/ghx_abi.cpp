@@ -1005,6 +1005,111 @@ int ghx_uput_create(const ghx_uput_entry* src, const ghx_uput_entry* dst, int32_
     });
 }
 
+int ghx_uself_create(const ghx_upack_entry* src, const ghx_upack_entry* dst, int32_t n, ghx_uself** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        *out = nullptr;
+        if (n < 0 || (n && (!src || !dst))) throw invalid("bad entry arrays");
+        *out = new ghx_uself{make_uself(src, dst, n)};
+        return GHX_OK;
+    });
+}
+
+int ghx_uself_execute(const ghx_uself* p, void* const* field_ptrs, int32_t n_fields,
+                      void* const* buffer_ptrs, int32_t n_buffers, ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        return p->p->execute_self(field_ptrs, n_fields, buffer_ptrs, n_buffers, stream);
+    });
+}
+
+int ghx_uself_info(const ghx_uself* p, uint64_t* bytes, int32_t* n_segments, int32_t* n_tiles)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (bytes) *bytes = p->p->bytes;
+        if (n_segments) *n_segments = int32_t(p->p->segs.size());
+        if (n_tiles) *n_tiles = int32_t(p->p->recs.size());
+        return GHX_OK;
+    });
+}
+
+int ghx_uself_segment(const ghx_uself* p, int32_t k, ghx_uself_segment_info* out)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        check_ptr(out, "out");
+        const uput_plan& u = *p->p;
+        if (k < 0 || size_t(k) >= u.segs.size()) throw invalid("segment index out of range");
+        const seg_up& s = u.segs[size_t(k)];
+        *out = ghx_uself_segment_info{};
+        out->src_field_off = s.src_field_off;
+        out->src_index_stride_b = s.src_index_stride_b;
+        out->src_level_stride_b = s.src_level_stride_b;
+        out->dst_field_off = s.dst_field_off;
+        out->dst_index_stride_b = s.dst_index_stride_b;
+        out->dst_level_stride_b = s.dst_level_stride_b;
+        out->first_index = u.first[size_t(k)];
+        out->bytes = s.bytes;
+        out->row_bytes = s.row_bytes;
+        out->tile_bytes = s.tile_bytes;
+        out->n = s.n;
+        out->message = u.message[size_t(k)];
+        out->n_segments = int32_t(u.segs.size());
+        out->src_slot = s.src_slot;
+        out->dst_slot = s.dst_slot;
+        out->mode = s.mode;
+        out->wlog2 = s.wlog2;
+        out->src_lid64 = s.src_lid64;
+        out->dst_lid64 = s.dst_lid64;
+        out->src_runs = s.src_runs;
+        out->dst_runs = s.dst_runs;
+        out->buf_slot = s.buf_slot;
+        out->buf_off = s.buf_off;
+        return GHX_OK;
+    });
+}
+
+int ghx_uself_destroy(ghx_uself* p)
+{
+    return guarded([&] {
+        delete p;
+        return GHX_OK;
+    });
+}
+
+int ghx_uexchange_self_info(const ghx_exchange* ex, int32_t* fusable, int32_t* n_segments,
+                            int32_t* n_tiles)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(fusable, "fusable");
+        const uput_plan* p = ex->uself.get();
+        *fusable = p ? 1 : 0;
+        if (n_segments) *n_segments = p ? int32_t(p->segs.size()) : 0;
+        if (n_tiles) *n_tiles = p ? int32_t(p->recs.size()) : 0;
+        if (!p) set_error(ex->uself_reason);
+        return GHX_OK;
+    });
+}
+
+int ghx_uexchange_self(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                       void* const* buffers, int32_t n_buffers, ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        if (!ex->uself) throw invalid("index-list self exchange: " + ex->uself_reason);
+        if (ex->dir_parity[0].word)
+            throw invalid("index-list self exchange: the send side has double-buffered buffers "
+                          "(ghx_exchange_set_parity); the fused launch writes one copy");
+        check_ptr(field_ptrs, "field_ptrs");
+        check_ptr(buffers, "buffers");
+        return ex->uself->execute_self(field_ptrs, n_fields, buffers, n_buffers, stream);
+    });
+}
+
 int ghx_uput_segment(const ghx_put* put, int32_t k, ghx_uput_segment_info* out)
 {
     return guarded([&] {

@@ -428,6 +428,50 @@ void build_cs_self(exchange_plan& ex, const ghx_cs_item* cs, int32_t me,
         refuse(e.what());
     }
 }
+
+// The fused self exchange of an exchange of unstructured items (uput_plan with its buffer side,
+// k_self_u), built device-less with the exchange; left absent, with the reason in
+// ex.uself_reason, when the exchange has a structured item, no message, a message that leaves
+// the rank, or what make_uself refuses. A message's unpack entry is the one at its pack entry's
+// (buffer slot, buffer offset): recv buffer i is send buffer i.
+void build_uself(exchange_plan& ex, int32_t me)
+{
+    const std::vector<ghx_upack_entry>& sent = ex.uentries[0];
+    const std::vector<ghx_upack_entry>& rent = ex.uentries[1];
+    auto refuse = [&](const std::string& why) {
+        ex.uself.reset();
+        ex.uself_reason = "not fusable: " + why;
+    };
+    if (ex.spack || ex.sunpack || !ex.entries[0].empty() || !ex.entries[1].empty())
+        return refuse("the exchange has structured items");
+    if (sent.empty() && rent.empty()) return refuse("the exchange has no message");
+    bool self = ex.send.size() == ex.recv.size();
+    for (size_t i = 0; self && i < ex.send.size(); ++i)
+        self = ex.send[i].first_id == ex.recv[i].first_id && ex.send[i].second_id == ex.recv[i].second_id &&
+               ex.send[i].size == ex.recv[i].size && ex.send[i].rank == me && ex.recv[i].rank == me;
+    if (!self) return refuse("the exchange has peer messages (a recv buffer that is not the send buffer of the same domain pair on this rank)");
+    std::map<std::pair<int32_t, uint64_t>, const ghx_upack_entry*> by_bytes;
+    for (const ghx_upack_entry& e : sent) by_bytes[{e.buffer_slot, e.buffer_offset}] = &e;
+    if (by_bytes.size() != sent.size() || sent.size() != rent.size())
+        return refuse("the pack and unpack entries do not pair one to one");
+    std::vector<ghx_upack_entry> src, dst;
+    for (const ghx_upack_entry& r : rent)
+    {
+        const auto it = by_bytes.find({r.buffer_slot, r.buffer_offset});
+        if (it == by_bytes.end()) return refuse("an unpack entry has no pack entry at the same buffer bytes");
+        src.push_back(*it->second);
+        dst.push_back(r);
+    }
+    try
+    {
+        ex.uself = make_uself(src.data(), dst.data(), int(src.size()));
+        ex.uself_reason.clear();
+    }
+    catch (const invalid& e)
+    {
+        refuse(e.what());
+    }
+}
 }  // namespace
 
 // The put plan of ghx_cs_put_create (cs_put_plan, k_put_cs): build_cs_self's pairing without the
@@ -604,6 +648,7 @@ std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, cons
     if (ex->cs_rotated == 0) build_mixed(*ex, items[0].pattern->my_rank, rent);
     if (cs) build_cs_self(*ex, cs, items[0].pattern->my_rank, rhalos);
     else ex->cs_self_reason = "not fusable: not a cubed-sphere exchange";
+    build_uself(*ex, items[0].pattern->my_rank);
     return ex;
 }
 

@@ -62,6 +62,10 @@ struct exchange_plan
     // (ghx_cs_exchange_self): null when it cannot be fused, cs_self_reason then says why
     std::unique_ptr<cs_self_plan> cs_self;
     std::string cs_self_reason;
+    // the fused self exchange of an exchange of unstructured items whose every message stays on
+    // this rank (ghx_uexchange_self, k_self_u): null when it cannot be fused, uself_reason says why
+    std::unique_ptr<uput_plan> uself;
+    std::string uself_reason;
 
     void make_split();  // the per-buffer plans (ghx_exchange_split)
 
@@ -131,6 +135,12 @@ struct ghx_put
     explicit ghx_put(std::unique_ptr<ghx::cs_put_plan> p);
     explicit ghx_put(std::unique_ptr<ghx::uput_plan> p);
     int execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const;
+};
+
+// The plan of ghx_uself_create: an index-list put plan with its buffer side (ghx::make_uself)
+struct ghx_uself
+{
+    std::unique_ptr<ghx::uput_plan> p;
 };
 
 namespace ghx

@@ -159,7 +159,9 @@ static_assert(sizeof(seg_u) == 96, "seg_u layout");
 // decomposition of the message bytes for both sides (mode, row_bytes, mag_*: as seg_u's). Message
 // row r = (i, l) by `mode` sits at field_off + lid[i] * index_stride_b + l * level_stride_b of
 // its side. A put has no buffer; its tile records are this record with the tile's index in
-// first_tile, one per workgroup.
+// first_tile, one per workgroup. The fused self exchange (k_self_u) uses the same record with the
+// message's place in its send buffer: message row r at buf_off + r * row_bytes of buffer buf_slot
+// in every mode (a put leaves both zero and never reads them).
 struct alignas(16) seg_up
 {
     const void* src_lids;      // device arrays, int32 or int64 per side
@@ -176,12 +178,15 @@ struct alignas(16) seg_up
     uint32_t tile_bytes;
     uint16_t src_slot, dst_slot;
     uint8_t wlog2;             // widest vector dividing the row and both sides' offsets and strides
+                               // (and buf_off, in a self exchange)
     uint8_t mode;              // as seg_u::mode, common to both sides
     uint8_t src_lid64, dst_lid64;
     uint8_t src_runs, dst_runs;  // the side's rows of consecutive lids are adjacent (4/8-B rows,
                                  // mode 0, index stride = row): it may move a 16-B chunk in one
                                  // access (put_runs); 2: at least half of its chunks are runs
-    uint8_t pad[14];
+    uint16_t buf_slot;         // self exchange: the send buffer of the message, and
+    uint8_t pad[4];
+    uint64_t buf_off;          // the byte offset of the segment's first row in it
 };
 static_assert(sizeof(seg_up) == 128, "seg_up layout");
 
@@ -333,6 +338,9 @@ int launch_self_cs(const kargs_cs& a, void* stream, uint32_t grid);
 int launch_put_cs(const kargs_pcs& a, void* stream, uint32_t grid);
 // tile_recs: seg_up records; field_ptr / buf_ptr: the source / target fields (as launch_put)
 int launch_put_u(const kargs& a, void* stream, uint32_t grid, bool runs);
+// tile_recs: seg_up records with their buffer side; field_ptr: the fields of both sides, buf_ptr:
+// the send buffers
+int launch_self_u(const kargs& a, void* stream, uint32_t grid, bool runs);
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

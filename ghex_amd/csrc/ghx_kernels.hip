@@ -1384,6 +1384,240 @@ __global__ __launch_bounds__(kBlock) void k_put_u(kargs a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Fused index-list self exchange (seg_up with its buffer side): send list on the sending field ->
+// the send buffer AND the receive list on the receiving field, no buffer byte read.
+// ---------------------------------------------------------------------------------------------
+
+// General path, the shape of put_tile_u: per loop trip a lane decodes its kU message positions
+// once, issues the kU index loads of the source table and the kU of the target table together,
+// then the kU value loads, the kU buffer stores (message position p at buf + p: consecutive lanes
+// at consecutive addresses, the coalesced side) and the kU target stores. A position past the
+// tile's end is clamped to the tile's last vector and moves the same bytes to the same two
+// addresses again. `buf` points at the segment's first message row.
+template<int W, bool S64, bool D64>
+__device__ __forceinline__ void self_tile_u(const seg_up& s, const char* __restrict__ src,
+                                            char* __restrict__ dst, char* __restrict__ buf,
+                                            uint32_t start, uint32_t end)
+{
+    using V = typename vec_t<W>::type;
+    const uint32_t last = end - W;  // tiles hold whole rows: end - start is a multiple of W
+    src += s.src_field_off;
+    dst += s.dst_field_off;
+    for (uint32_t base = start + threadIdx.x * W; base < end; base += kU * kBlock * W)
+    {
+        uint32_t pos[kU], idx[kU], lev[kU], rem[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) pos[u] = min(base + uint32_t(u) * kBlock * W, last);
+        if (s.mode == 0)
+        {
+#pragma unroll
+            for (int u = 0; u < kU; ++u)
+            {
+                idx[u] = fastdiv(pos[u], s.mag_row);
+                lev[u] = 0;
+                rem[u] = pos[u] - idx[u] * s.row_bytes;
+            }
+        }
+        else if (s.mode == 1)
+        {
+#pragma unroll
+            for (int u = 0; u < kU; ++u)
+            {
+                const uint32_t row = fastdiv(pos[u], s.mag_row);
+                idx[u] = fastdiv(row, s.mag_inner);
+                lev[u] = row - idx[u] * s.row_levels;
+                rem[u] = pos[u] - row * s.row_bytes;
+            }
+        }
+        else
+        {
+#pragma unroll
+            for (int u = 0; u < kU; ++u)
+            {
+                const uint32_t row = fastdiv(pos[u], s.mag_row);
+                lev[u] = fastdiv(row, s.mag_inner);
+                idx[u] = row - lev[u] * s.n;
+                rem[u] = pos[u] - row * s.row_bytes;
+            }
+        }
+        int64_t sl[kU], dl[kU];
+        gather_lids<S64>(s.src_lids, idx, sl);
+        gather_lids<D64>(s.dst_lids, idx, dl);
+        V v[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+            v[u] = vload<V>(src + sl[u] * s.src_index_stride_b + int64_t(lev[u]) * s.src_level_stride_b + rem[u]);
+#pragma unroll
+        for (int u = 0; u < kU; ++u) vstore<V>(buf + pos[u], v[u]);
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+            vstore<V>(dst + dl[u] * s.dst_index_stride_b + int64_t(lev[u]) * s.dst_level_stride_b + rem[u], v[u]);
+    }
+}
+
+template<bool S64, bool D64>
+__device__ __forceinline__ void self_tile_u_w(const seg_up& s, const char* src, char* dst, char* buf,
+                                              uint32_t start, uint32_t end, int w)
+{
+    switch (w)
+    {
+        case 4: self_tile_u<16, S64, D64>(s, src, dst, buf, start, end); break;
+        case 3: self_tile_u<8, S64, D64>(s, src, dst, buf, start, end); break;
+        case 2: self_tile_u<4, S64, D64>(s, src, dst, buf, start, end); break;
+        case 1: self_tile_u<2, S64, D64>(s, src, dst, buf, start, end); break;
+        default: self_tile_u<1, S64, D64>(s, src, dst, buf, start, end); break;
+    }
+}
+
+// Run path, the shape of put_runs: rows of L = 4 or 8 bytes (mode 0), a lane owns a 16-byte
+// message chunk (K = 16 / L rows) and loads its K lids of each table with one vector load. Each
+// field side decides on its own whether its chunk is ONE 16-byte access (its K lids a run, its
+// rows adjacent) or K row accesses; the buffer side is always ONE 16-byte store at buf + p (the
+// launch takes this path only where every chunk of the buffer is 16-B aligned). A segment tail
+// of fewer than K rows goes row by row on all three sides; no lid is read at or beyond n.
+template<int L>
+__device__ __forceinline__ void self_runs(const seg_up& s, const char* __restrict__ src,
+                                          char* __restrict__ dst, char* __restrict__ buf,
+                                          uint32_t start, uint32_t end)
+{
+    using V = typename vec_t<16>::type;
+    using R = typename vec_t<L>::type;
+    constexpr int K = 16 / L;
+    src += s.src_field_off;
+    dst += s.dst_field_off;
+    for (uint32_t base = start + threadIdx.x * 16; base < end; base += kU * kBlock * 16)
+    {
+        int64_t so[kU][K], to[kU][K];
+        uint32_t full = 0, srun = 0, drun = 0;  // bit u: chunk u holds K rows / its side is a run
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+        {
+            const uint32_t p = base + u * kBlock * 16;
+            if (p >= end) continue;
+            const uint32_t r0 = p / L;
+            int64_t ls[K], ld[K];
+            if (p + 16 <= end)
+            {
+                full |= 1u << u;
+                load_lid_chunk<K>(s.src_lids, s.src_lid64, r0, ls);
+                load_lid_chunk<K>(s.dst_lids, s.dst_lid64, r0, ld);
+                bool cs = s.src_runs != 0, cd = s.dst_runs != 0;
+#pragma unroll
+                for (int j = 1; j < K; ++j)
+                {
+                    cs = cs && ls[j] == ls[0] + j;
+                    cd = cd && ld[j] == ld[0] + j;
+                }
+                if (cs) srun |= 1u << u;
+                if (cd) drun |= 1u << u;
+            }
+            else
+            {
+#pragma unroll
+                for (int j = 0; j < K; ++j)
+                {
+                    const bool in = p + j * L < end;
+                    ls[j] = in ? load_lid_one(s.src_lids, s.src_lid64, r0 + j) : 0;
+                    ld[j] = in ? load_lid_one(s.dst_lids, s.dst_lid64, r0 + j) : 0;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+            {
+                so[u][j] = ls[j] * s.src_index_stride_b;
+                to[u][j] = ld[j] * s.dst_index_stride_b;
+            }
+        }
+        V v[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+        {
+            if (!(full >> u & 1u)) continue;
+            if (srun >> u & 1u)
+            {
+                const v4_a4 x = vload<v4_a4>(src + so[u][0]);
+                v[u] = V{x.x, x.y, x.z, x.w};
+            }
+            else
+            {
+                R w[K];
+#pragma unroll
+                for (int j = 0; j < K; ++j) w[j] = vload<R>(src + so[u][j]);
+                v[u] = assemble<L>(w);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+            if (full >> u & 1u) vstore<V>(buf + (base + u * kBlock * 16), v[u]);
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+        {
+            const uint32_t p = base + u * kBlock * 16;
+            if (p >= end) continue;
+            if (!(full >> u & 1u))
+            {
+                // segment tail: fewer than K rows left, row by row
+#pragma unroll
+                for (int j = 0; j < K; ++j)
+                {
+                    if (p + j * L >= end) break;
+                    const R x = vload<R>(src + so[u][j]);
+                    vstore<R>(buf + (p + j * L), x);
+                    vstore<R>(dst + to[u][j], x);
+                }
+                continue;
+            }
+            if (drun >> u & 1u)
+                vstore<v4_a4>(dst + to[u][0], v4_a4{v[u].x, v[u].y, v[u].z, v[u].w});
+            else
+            {
+                R w[K];
+                split<L>(v[u], w);
+#pragma unroll
+                for (int j = 0; j < K; ++j) vstore<R>(dst + to[u][j], w[j]);
+            }
+        }
+    }
+}
+
+// One tile record per workgroup at its block index (grid-stride beyond the grid cap). RUNS: every
+// segment of the plan takes the run path (uput_plan::execute_self decides with the launch's
+// pointers). Field slot f of either side at field_ptr[f], buffer slot b at buf_ptr[b].
+template<bool RUNS>
+__global__ __launch_bounds__(kBlock) void k_self_u(kargs a)
+{
+    const seg_up* __restrict__ recs = static_cast<const seg_up*>(a.tile_recs);
+    for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x)
+    {
+        const seg_up s = recs[t];
+        const uint32_t start = s.first_tile * s.tile_bytes;
+        const uint32_t end = min(start + s.tile_bytes, s.bytes);
+        const char* src = reinterpret_cast<const char*>(a.field_ptr[s.src_slot]);
+        char* dst = reinterpret_cast<char*>(a.field_ptr[s.dst_slot]);
+        char* buf = reinterpret_cast<char*>(a.buf_ptr[s.buf_slot] + s.buf_off);
+        if constexpr (RUNS)
+        {
+            if (s.row_bytes == 8) self_runs<8>(s, src, dst, buf, start, end);
+            else self_runs<4>(s, src, dst, buf, start, end);
+        }
+        else
+        {
+            int w = s.wlog2;
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(src)));
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(dst)));
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
+            if (s.src_lid64)
+            {
+                if (s.dst_lid64) self_tile_u_w<true, true>(s, src, dst, buf, start, end, w);
+                else self_tile_u_w<true, false>(s, src, dst, buf, start, end, w);
+            }
+            else if (s.dst_lid64) self_tile_u_w<false, true>(s, src, dst, buf, start, end, w);
+            else self_tile_u_w<false, false>(s, src, dst, buf, start, end, w);
+        }
+    }
+}
+
 int launched(const char* what)
 {
     const hipError_t e = hipGetLastError();
@@ -1520,6 +1754,15 @@ int launch_put_u(const kargs& a, void* stream, uint32_t grid, bool runs)
     if (runs) launch(k_put_u<true>, grid, static_cast<hipStream_t>(stream), a);
     else launch(k_put_u<false>, grid, static_cast<hipStream_t>(stream), a);
     return launched("index-list put");
+}
+
+int launch_self_u(const kargs& a, void* stream, uint32_t grid, bool runs)
+{
+    if (a.n_tiles == 0) return GHX_OK;
+    grid = min(grid, a.n_tiles);
+    if (runs) launch(k_self_u<true>, grid, static_cast<hipStream_t>(stream), a);
+    else launch(k_self_u<false>, grid, static_cast<hipStream_t>(stream), a);
+    return launched("index-list self-exchange");
 }
 
 template<bool DBL, bool REC>

@@ -1120,7 +1120,8 @@ int uplan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* s
 // ---------------------------------------------------------------------------------------------
 // index-list put
 // ---------------------------------------------------------------------------------------------
-uput_plan::uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n_entries)
+uput_plan::uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n_entries,
+                     const ubuf_place* buf)
 {
     auto mag = [](int64_t v) { return uint64_t(v < 0 ? -v : v); };
     // both sides' index lists in one device allocation: int32 where a list fits, per list
@@ -1183,6 +1184,7 @@ uput_plan::uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n
                           "(list lengths, element sizes, levels or level order differ)");
         max_src_slot = std::max(max_src_slot, se.field_slot);
         max_dst_slot = std::max(max_dst_slot, de.field_slot);
+        if (buf) max_buf_slot = std::max(max_buf_slot, buf[e].slot);
         const bool swide = wide_list(se), dwide = wide_list(de);
         const int64_t elem = sd.elem_size;
         const int64_t per_index = int64_t(sd.levels) * elem;
@@ -1233,6 +1235,13 @@ uput_plan::uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n
             {
                 w = std::min(w, wlog2_of(mag(s.src_level_stride_b)));
                 w = std::min(w, wlog2_of(mag(s.dst_level_stride_b)));
+            }
+            if (buf)
+            {
+                // the segment's first message row in the send buffer, where uplan's pack puts it
+                s.buf_slot = uint16_t(buf[e].slot);
+                s.buf_off = buf[e].off + uint64_t(lev >= 0 ? (lev * se.n_lids + a) * elem : a * per_index);
+                w = std::min(w, wlog2_of(s.buf_off));
             }
             s.wlog2 = uint8_t(w);
             const bool chunked = g_tune.urun && m == 0 && (Ls == 4 || Ls == 8);
@@ -1343,6 +1352,83 @@ int uput_plan::execute(void* const* src, int ns, void* const* dst, int nd, void*
         runs = a.field_ptr[segs[k].src_slot] % segs[k].row_bytes == 0 &&
                a.buf_ptr[segs[k].dst_slot] % segs[k].row_bytes == 0;
     return launch_put_u(a, stream, grid_for_tiles(a.n_tiles), runs);
+}
+
+// ---------------------------------------------------------------------------------------------
+// fused index-list self exchange
+// ---------------------------------------------------------------------------------------------
+int uput_plan::execute_self(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
+{
+    if (recs.empty()) return GHX_OK;
+    const int nfs = std::max(max_src_slot, max_dst_slot);
+    if (!fptr || !bptr || nf <= nfs || nb <= max_buf_slot)
+        throw invalid("pointer arrays do not cover the plan's slots");
+    if (!dev.recs || !dev.lids) throw hip_error("plan has no device tables (no HIP device at creation)");
+    kargs a{};
+    a.tile_recs = dev.recs;
+    a.n_tiles = uint32_t(recs.size());
+    fill_slots(a.field_ptr, fptr, {}, nfs + 1, "field");
+    fill_slots(a.buf_ptr, bptr, {}, max_buf_slot + 1, "buffer");
+    // the run-path kernel when every segment qualifies with these pointers: both fields aligned
+    // to the row, every message chunk of the buffer 16-B aligned
+    bool runs = run_ok;
+    for (size_t k = 0; runs && k < segs.size(); ++k)
+        runs = a.field_ptr[segs[k].src_slot] % segs[k].row_bytes == 0 &&
+               a.field_ptr[segs[k].dst_slot] % segs[k].row_bytes == 0 &&
+               (a.buf_ptr[segs[k].buf_slot] + segs[k].buf_off) % 16 == 0;
+    return launch_self_u(a, stream, grid_for_tiles(a.n_tiles), runs);
+}
+
+std::unique_ptr<uput_plan> make_uself(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n)
+{
+    const size_t nk = n > 0 ? size_t(n) : 0;
+    std::vector<ghx_uput_entry> se(nk), de(nk);
+    std::vector<ubuf_place> place(nk);
+    for (int k = 0; k < n; ++k)
+    {
+        const ghx_upack_entry &s = src[k], &d = dst[k];
+        if (s.field_slot < 0 || d.field_slot < 0 || s.buffer_slot < 0 || d.buffer_slot < 0)
+            throw invalid("negative slot");
+        if (s.field_slot >= GHX_MAX_SLOTS || d.field_slot >= GHX_MAX_SLOTS || s.buffer_slot >= GHX_MAX_SLOTS)
+            throw invalid("a fused index-list self exchange takes at most 64 field and 64 buffer "
+                          "slots (one launch, no launch groups)");
+        if (s.buffer_slot != d.buffer_slot || s.buffer_offset != d.buffer_offset)
+            throw invalid("the pack and the unpack entry of a message differ in buffer slot or "
+                          "buffer offset (they do not name the same buffer bytes)");
+        se[size_t(k)] = {s.data, s.field_slot, s.lids, s.n_lids};
+        de[size_t(k)] = {d.data, d.field_slot, d.lids, d.n_lids};
+        place[size_t(k)] = {s.buffer_slot, s.buffer_offset};
+    }
+    // descriptors, lids and the agreement of the two sides: the put's checks
+    auto p = std::make_unique<uput_plan>(se.data(), de.data(), n, place.data());
+    // no two messages share buffer bytes
+    std::vector<std::pair<std::pair<int32_t, uint64_t>, uint64_t>> ranges;  // (slot, first), end
+    for (int k = 0; k < n; ++k)
+    {
+        const uint64_t nb = uint64_t(src[k].n_lids) * uint64_t(src[k].data.levels) * uint64_t(src[k].data.elem_size);
+        if (nb) ranges.push_back({{src[k].buffer_slot, src[k].buffer_offset}, src[k].buffer_offset + nb});
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); ++i)
+        if (ranges[i].first.first == ranges[i - 1].first.first && ranges[i].first.second < ranges[i - 1].second)
+            throw invalid("two messages overlap in one buffer");
+    // A fused launch reads and writes in no defined order: it equals pack followed by unpack only
+    // if no cell (field slot, lid) is read and written, and none is written twice.
+    std::vector<std::pair<int32_t, int64_t>> reads, writes;
+    for (int k = 0; k < n; ++k)
+        for (int64_t i = 0; i < src[k].n_lids; ++i)
+        {
+            reads.emplace_back(src[k].field_slot, src[k].lids[i]);
+            writes.emplace_back(dst[k].field_slot, dst[k].lids[i]);
+        }
+    std::sort(writes.begin(), writes.end());
+    if (std::adjacent_find(writes.begin(), writes.end()) != writes.end())
+        throw invalid("a target cell of a field slot appears twice (the launch's stores have no order)");
+    for (const auto& c : reads)
+        if (std::binary_search(writes.begin(), writes.end(), c))
+            throw invalid("a cell of a field slot is both a source and a target of the plan (the "
+                          "launch's loads and stores have no order)");
+    return p;
 }
 
 }  // namespace ghx

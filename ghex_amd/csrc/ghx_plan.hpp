@@ -222,10 +222,21 @@ struct uplan
 // workgroup. Field slots: the sender's index the source pointer array, the receiver's the
 // target pointer array; fewer than GHX_MAX_SLOTS of each (one launch). Built without a device;
 // the records are kept on the host for inspection and uploaded when there is a device.
+//
+// The fused index-list self exchange (k_self_u, make_uself) is the same plan with a buffer side:
+// `buf[k]` places message k in a send buffer, the segments carry their buffer slot and offset
+// (which narrows wlog2 like any other offset), and both sides' field slots index ONE pointer
+// array. execute_self stores every value to the buffer and to the target field in one launch.
+struct ubuf_place
+{
+    int32_t slot;
+    uint64_t off;
+};
 struct uput_plan
 {
     uint64_t bytes = 0;            // message bytes moved per execution
     int max_src_slot = -1, max_dst_slot = -1;
+    int max_buf_slot = -1;         // -1: a put (no buffer side)
     std::vector<seg_up> segs;      // plan order, first_tile 0
     std::vector<int32_t> message;  // per segment: its message, and
     std::vector<int64_t> first;    // its first position in that message's lists
@@ -233,9 +244,16 @@ struct uput_plan
     bool run_ok = false;           // every segment may take the run path (urun on, mode 0, rows
                                    // of 4 or 8 B, tiles of whole 16-B chunks)
     device_tables dev;             // recs: the tile records; lids: both sides' index lists
-    uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n);
+    uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n,
+              const ubuf_place* buf = nullptr);
     int execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const;
+    // a plan with a buffer side: fields (both sides' slots) and send buffers, ONE launch
+    int execute_self(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
+// The plan of ghx_uself_create: src[k] / dst[k] are the pack and the unpack entry of the same
+// message bytes. Throws `invalid` with the reason for what one fused launch cannot serve or would
+// not do exactly as pack followed by unpack does (see include/ghx.h).
+std::unique_ptr<uput_plan> make_uself(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n);
 
 // The per-call entry points' plans, cached by content (ghx_cache.cpp): the plan of the call's
 // descriptor and spaces, or index list, is built on first use and executed on `stream`.

@@ -10,8 +10,10 @@ from .communication_object import CommunicationObject
 from .pattern import PatternContainer
 
 
-def make_communication_object(context, **options) -> CommunicationObject:
-    return CommunicationObject(context, **options)
+def make_communication_object(context, fuse_lists: bool = False, **options) -> CommunicationObject:
+    """fuse_lists: when every message of an exchange stays on this rank, pack and unpack run as
+    ONE launch (ghx_uexchange_self); an exchange that cannot be fused takes the usual path."""
+    return CommunicationObject(context, fuse_lists=fuse_lists, **options)
 
 
 class DomainDescriptor:

@@ -743,6 +743,80 @@ typedef struct ghx_uput_segment_info
 } ghx_uput_segment_info;
 int ghx_uput_segment(const ghx_put* put, int32_t k, ghx_uput_segment_info* out);
 
+/* The fused self exchange of index lists (no reference counterpart: the reference packs, sends to
+ * self and unpacks, communication_object.hpp:703-767). src[k] is message k's pack entry (the
+ * sender's field, its send list, buffer_slot and buffer_offset) and dst[k] the unpack entry of
+ * the SAME message bytes (the receiver's field, its receive list; buffer_slot and buffer_offset
+ * equal src[k]'s). The field slots of both sides index ONE field pointer array (an exchange's
+ * items). One execution loads, for every message, i < n_lids and l < levels, the value from the
+ * source field once and stores it to the buffer where a ghx_uplan pack of src writes it and to
+ * the target cell a ghx_uplan unpack of dst writes: byte for byte what pack followed by unpack
+ * leaves in the buffers and the fields, as ONE launch (k_self_u) that reads no buffer byte. Pad
+ * bytes between entries are not written. Execution is stream-ordered, never allocates and can be
+ * captured. The row decomposition is ghx_uput_create's, one per message for both sides (mode 0
+ * only where the levels are contiguous on both); message row r sits at
+ * buffer_offset + r * row_bytes in every mode; lists beyond 2^30 bytes split as theirs do; the
+ * vector width is also narrowed by buffer_offset and, at launch, by buffer pointer + offset.
+ * Messages of 4- or 8-byte rows move 16 bytes per lane (knob "urun") when every buffer pointer +
+ * offset is 16-byte aligned and both field pointers are aligned to the row: the buffer side is
+ * then one 16-byte store, each field side as in ghx_uput_create.
+ * Created without a device like every other plan (execution then reports GHX_ERR_HIP).
+ * GHX_ERR_INVALID, with the reason in ghx_last_error(), when: the two sides of a message differ
+ * in n_lids, elem_size, levels or levels_first, or in buffer_slot or buffer_offset; two messages'
+ * byte ranges overlap in one buffer; a lid is negative; elem_size < 1 or levels < 1; a field or
+ * buffer slot is negative or >= 64 (one launch, no launch groups); a row is longer than 1 GiB;
+ * a cell (field slot, lid) is both a source and a target of the plan; a target cell appears
+ * twice. The last two are what makes a launch whose loads and stores have no order equal to the
+ * two-launch exchange exactly; patterns always pass them (send lists hold inner cells, receive
+ * lists distinct outer cells). Source lids may repeat. Two slots given the same pointer stay the
+ * caller's contract. */
+typedef struct ghx_uself ghx_uself;
+int ghx_uself_create(const ghx_upack_entry* src, const ghx_upack_entry* dst, int32_t n, ghx_uself** out);
+int ghx_uself_execute(const ghx_uself* p, void* const* field_ptrs, int32_t n_fields,
+                      void* const* buffer_ptrs, int32_t n_buffers, ghx_stream stream);
+/* message bytes per execution, segments, workgroup tiles */
+int ghx_uself_info(const ghx_uself* p, uint64_t* bytes, int32_t* n_segments, int32_t* n_tiles);
+/* Segment k of a plan of ghx_uself_create (host only): ghx_uput_segment_info's fields with the
+ * same meaning, then the segment's place in its buffer: its first message row at buf_off of
+ * buffer buf_slot (wlog2 is narrowed by buf_off as well). GHX_ERR_INVALID for k out of range. */
+typedef struct ghx_uself_segment_info
+{
+    int64_t src_field_off, src_index_stride_b, src_level_stride_b;
+    int64_t dst_field_off, dst_index_stride_b, dst_level_stride_b;
+    int64_t first_index;
+    uint32_t bytes;
+    uint32_t row_bytes;
+    uint32_t tile_bytes;
+    uint32_t n;
+    int32_t message;
+    int32_t n_segments;                /* of the whole plan */
+    int32_t src_slot, dst_slot;
+    int32_t mode;
+    int32_t wlog2;
+    int32_t src_lid64, dst_lid64;
+    int32_t src_runs, dst_runs;
+    int32_t buf_slot;
+    uint64_t buf_off;
+} ghx_uself_segment_info;
+int ghx_uself_segment(const ghx_uself* p, int32_t k, ghx_uself_segment_info* out);
+int ghx_uself_destroy(ghx_uself* p);
+
+/* The fused self exchange of an exchange of unstructured items. ghx_exchange_create also plans
+ * ONE launch (a ghx_uself over the exchange's pack and unpack entries, paired by buffer slot and
+ * buffer offset) when the exchange has unstructured items only and at least one message, every
+ * buffer of both directions belongs to this rank, recv buffer i is send buffer i (same domain
+ * pair, same size), and ghx_uself_create's conditions hold (at most 64 items and 64 buffers among
+ * them). ghx_uexchange_self_info works without a device; with *fusable = 0, ghx_last_error()
+ * holds the reason. ghx_uexchange_self has ghx_exchange_self's argument contract (the buffers are
+ * the send buffers, which hold the packed message afterwards) and fails with GHX_ERR_INVALID on
+ * an exchange that is not fusable or whose send side has parity set (ghx_exchange_set_parity,
+ * direction 0). ghx_exchange_self_fusable, ghx_exchange_mixed and ghx_cs_self_info are unchanged
+ * by it: an exchange of unstructured items still reports 0 there. */
+int ghx_uexchange_self_info(const ghx_exchange* ex, int32_t* fusable, int32_t* n_segments,
+                            int32_t* n_tiles);
+int ghx_uexchange_self(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                       void* const* buffers, int32_t n_buffers, ghx_stream stream);
+
 /* Device-side access epochs of the zero-copy exchanges (bulk puts, direct pack): the reference's
  * access guards (include/ghex/rma/access_guard.hpp:35-140; per range: start/end_target_epoch on
  * the owner, start/end_source_epoch on the putter; include/ghex/bulk_communication_object.hpp
