@@ -139,6 +139,12 @@ _SIGS = {
     "ghx_uself_destroy": (c_i32, [c_vp]),
     "ghx_uexchange_self_info": (c_i32, [c_vp, P(c_i32), P(c_i32), P(c_i32)]),
     "ghx_uexchange_self": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_umixed_create": (c_i32, [P(UPackEntry), P(UPackEntry), c_i32, P(UPackEntry), c_i32, P(c_vp)]),
+    "ghx_umixed_info": (c_i32, [c_vp, P(c_i32), P(c_i32), P(c_i32)]),
+    "ghx_umixed_peer_segment": (c_i32, [c_vp, c_i32, P(USegmentInfo)]),
+    "ghx_uexchange_mixed_info": (c_i32, [c_vp, P(c_i32), P(c_i32), P(c_i32)]),
+    "ghx_uexchange_pack_self": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_uexchange_unpack_peers": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
                               c_i32, c_vp]),
     "ghx_udomain_create": (c_i32, [c_i32, P(c_i64), c_i64, P(c_i64), c_i64, P(c_vp)]),

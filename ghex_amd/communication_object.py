@@ -252,7 +252,7 @@ class CommunicationObject:
     def __init__(self, context, fuse_self: bool = True, staging=None, pipelined: bool = False,
                  rccl_self: bool = False, max_streams: int = 4, copy_engine: str = "probe",
                  direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False,
-                 fuse_lists: bool = False):
+                 fuse_lists: bool = False, fuse_lists_mixed: bool = False):
         if staging not in (None, "host"):
             raise ValueError("staging must be None (device buffers) or 'host'")
         if direct and (staging is not None or pipelined or rccl_self):
@@ -279,6 +279,10 @@ class CommunicationObject:
         # unstructured fields, every message on this rank: pack and unpack in one launch
         # (ghx_uexchange_self). Opt-in; a plan that cannot be fused takes the usual path
         self.fuse_lists = bool(fuse_lists)
+        # unstructured fields, self AND peer messages: the pack launch also completes the self
+        # messages, the unpack launch covers the peers only (ghx_uexchange_pack_self,
+        # ghx_uexchange_unpack_peers). Opt-in; a plan without that form takes the usual path
+        self.fuse_lists_mixed = bool(fuse_lists_mixed)
         self.staging = staging
         self.pipelined = pipelined
         # tests: route the self messages through RCCL too (a 1-rank communicator), so the
@@ -327,6 +331,16 @@ class CommunicationObject:
             _ghx.call("ghx_uexchange_self_info", plan.h, ctypes.byref(f), None, None)
             plan._lists_self = bool(f.value)
         return plan._lists_self
+
+    def lists_mixed(self, plan) -> bool:
+        """An exchange of unstructured fields with self AND peer messages which libghx has planned
+        in the mixed form (ghx_uexchange_mixed_info): ghx_uexchange_pack_self packs every send
+        buffer and completes the self messages, ghx_uexchange_unpack_peers unpacks the rest."""
+        if getattr(plan, "_lists_mixed", None) is None:
+            f = ctypes.c_int32()
+            _ghx.call("ghx_uexchange_mixed_info", plan.h, ctypes.byref(f), None, None)
+            plan._lists_mixed = bool(f.value)
+        return plan._lists_mixed
 
     def mixed(self, plan) -> bool:
         """Self AND peer messages: the pack launch also completes the self messages
@@ -531,8 +545,12 @@ class CommunicationObject:
             return CommunicationHandle(self, stream, self._done_event(stream))
         with torch.cuda.stream(stream):
             mixed = self.fuse_self and self.mixed(plan)
-            _ghx.call("ghx_exchange_pack_self" if mixed else "ghx_exchange_pack", plan.h,
-                      fptrs, len(bis), sptrs, len(send), stream.cuda_stream)
+            pack, unpack = (("ghx_exchange_pack_self", "ghx_exchange_unpack_peers") if mixed else
+                            ("ghx_exchange_pack", "ghx_exchange_unpack"))
+            if self.fuse_self and self.fuse_lists_mixed and self.lists_mixed(plan):
+                # index lists, self and peer messages: the pack also completes the self messages
+                pack, unpack = "ghx_uexchange_pack_self", "ghx_uexchange_unpack_peers"
+            _ghx.call(pack, plan.h, fptrs, len(bis), sptrs, len(send), stream.cuda_stream)
             me = self.context.rank()
             sends = [(x["rank"], x["tag"], send[i][:x["size"]])
                      for i, x in enumerate(plan.send) if x["rank"] != me]
@@ -543,8 +561,7 @@ class CommunicationObject:
             else:
                 for w in route(self.context, sends, recvs):
                     w.wait()  # NCCL: the stream waits for the recvs, the host does not
-            _ghx.call("ghx_exchange_unpack_peers" if mixed else "ghx_exchange_unpack",
-                      plan.h, fptrs, len(bis), rptrs, len(recv), stream.cuda_stream)
+            _ghx.call(unpack, plan.h, fptrs, len(bis), rptrs, len(recv), stream.cuda_stream)
             ev = self._done_event(stream)
         return CommunicationHandle(self, stream, ev)
 
@@ -901,6 +918,28 @@ class CommunicationObject:
         send, recv = self.buffers(plan, bis[0].field.device)
         s = (stream or torch.cuda.current_stream()).cuda_stream
         _ghx.call("ghx_exchange_unpack_peers", plan.h,
+                  _ghx.ptr_array([b.field.data_ptr() for b in bis]), len(bis),
+                  _ghx.ptr_array([t.data_ptr() for t in recv]), len(recv), s)
+        return plan, send, recv
+
+    def pack_lists_self_only(self, bis, stream=None):
+        """Index-list mixed exchanges: pack every send buffer and complete the self messages."""
+        import torch
+        plan = self._plain_plan(bis)
+        send, recv = self.buffers(plan, bis[0].field.device)
+        s = (stream or torch.cuda.current_stream()).cuda_stream
+        _ghx.call("ghx_uexchange_pack_self", plan.h,
+                  _ghx.ptr_array([b.field.data_ptr() for b in bis]), len(bis),
+                  _ghx.ptr_array([t.data_ptr() for t in send]), len(send), s)
+        return plan, send, recv
+
+    def unpack_list_peers_only(self, bis, stream=None):
+        """Index-list mixed exchanges: unpack the peer messages only."""
+        import torch
+        plan = self._plain_plan(bis)
+        send, recv = self.buffers(plan, bis[0].field.device)
+        s = (stream or torch.cuda.current_stream()).cuda_stream
+        _ghx.call("ghx_uexchange_unpack_peers", plan.h,
                   _ghx.ptr_array([b.field.data_ptr() for b in bis]), len(bis),
                   _ghx.ptr_array([t.data_ptr() for t in recv]), len(recv), s)
         return plan, send, recv

@@ -292,35 +292,44 @@ int ghx_uplan_info(const ghx_uplan* plan, uint64_t* bytes, int32_t* n_segments, 
     });
 }
 
+namespace
+{
+// segment k of an index-list plan (ghx_uplan_segment, ghx_umixed_peer_segment)
+void usegment_info(const uplan* plan, int32_t k, ghx_usegment_info* out)
+{
+    if (k < 0 || k >= plan->n_segments) throw invalid("segment index out of range");
+    // the host copies of the launch groups, in plan order (as ghx_plan_segment)
+    size_t i = size_t(k), g = 0;
+    while (g < plan->groups.size() && i >= plan->groups[g].host_segs.size())
+        i -= plan->groups[g++].host_segs.size();
+    if (g == plan->groups.size()) throw invalid("segment index out of range");
+    const launch_group<seg_u>& grp = plan->groups[g];
+    const seg_u& s = grp.host_segs[i];
+    *out = ghx_usegment_info{};
+    out->field_off = s.field_off;
+    out->buf_off = s.buf_off;
+    out->index_stride_b = s.index_stride_b;
+    out->level_stride_b = s.level_stride_b;
+    out->bytes = s.bytes;
+    out->row_bytes = s.row_bytes;
+    out->tile_bytes = s.tile_bytes;
+    out->n = s.n;
+    out->field_slot = grp.fmap.empty() ? int32_t(s.field_slot) : grp.fmap[s.field_slot];
+    out->buffer_slot = grp.bmap.empty() ? int32_t(s.buf_slot) : grp.bmap[s.buf_slot];
+    out->mode = s.mode;
+    out->wlog2 = s.wlog2;
+    out->lid64 = s.lid64;
+    out->runs = s.runs;
+    out->fpol = s.fpol;
+}
+}  // namespace
+
 int ghx_uplan_segment(const ghx_uplan* plan, int32_t k, ghx_usegment_info* out)
 {
     return guarded([&] {
         check_ptr(plan, "plan");
         check_ptr(out, "out");
-        if (k < 0 || k >= plan->n_segments) throw invalid("segment index out of range");
-        // the host copies of the launch groups, in plan order (as ghx_plan_segment)
-        size_t i = size_t(k), g = 0;
-        while (g < plan->groups.size() && i >= plan->groups[g].host_segs.size())
-            i -= plan->groups[g++].host_segs.size();
-        if (g == plan->groups.size()) throw invalid("segment index out of range");
-        const launch_group<seg_u>& grp = plan->groups[g];
-        const seg_u& s = grp.host_segs[i];
-        *out = ghx_usegment_info{};
-        out->field_off = s.field_off;
-        out->buf_off = s.buf_off;
-        out->index_stride_b = s.index_stride_b;
-        out->level_stride_b = s.level_stride_b;
-        out->bytes = s.bytes;
-        out->row_bytes = s.row_bytes;
-        out->tile_bytes = s.tile_bytes;
-        out->n = s.n;
-        out->field_slot = grp.fmap.empty() ? int32_t(s.field_slot) : grp.fmap[s.field_slot];
-        out->buffer_slot = grp.bmap.empty() ? int32_t(s.buf_slot) : grp.bmap[s.buf_slot];
-        out->mode = s.mode;
-        out->wlog2 = s.wlog2;
-        out->lid64 = s.lid64;
-        out->runs = s.runs;
-        out->fpol = s.fpol;
+        usegment_info(plan, k, out);
         return GHX_OK;
     });
 }
@@ -1029,9 +1038,44 @@ int ghx_uself_info(const ghx_uself* p, uint64_t* bytes, int32_t* n_segments, int
 {
     return guarded([&] {
         check_ptr(p, "plan");
-        if (bytes) *bytes = p->p->bytes;
-        if (n_segments) *n_segments = int32_t(p->p->segs.size());
-        if (n_tiles) *n_tiles = int32_t(p->p->recs.size());
+        const uplan* peers = p->p->peers.get();  // the mixed form: both parts
+        if (bytes) *bytes = p->p->bytes + (peers ? peers->bytes : 0);
+        if (n_segments) *n_segments = int32_t(p->p->segs.size()) + (peers ? peers->n_segments : 0);
+        if (n_tiles) *n_tiles = int32_t(p->p->recs.size() + p->p->peer_recs.size());
+        return GHX_OK;
+    });
+}
+
+int ghx_umixed_create(const ghx_upack_entry* src, const ghx_upack_entry* dst, int32_t n_self,
+                      const ghx_upack_entry* peers, int32_t n_peers, ghx_uself** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        *out = nullptr;
+        *out = new ghx_uself{make_umixed(src, dst, n_self, peers, n_peers)};
+        return GHX_OK;
+    });
+}
+
+int ghx_umixed_info(const ghx_uself* p, int32_t* n_self_tiles, int32_t* n_peer_segments,
+                    int32_t* n_peer_tiles)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (n_self_tiles) *n_self_tiles = int32_t(p->p->recs.size());
+        if (n_peer_segments) *n_peer_segments = p->p->peers ? p->p->peers->n_segments : 0;
+        if (n_peer_tiles) *n_peer_tiles = int32_t(p->p->peer_recs.size());
+        return GHX_OK;
+    });
+}
+
+int ghx_umixed_peer_segment(const ghx_uself* p, int32_t k, ghx_usegment_info* out)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        check_ptr(out, "out");
+        if (!p->p->peers) throw invalid("the plan has no peer part (ghx_uself_create's plan)");
+        usegment_info(p->p->peers.get(), k, out);
         return GHX_OK;
     });
 }
@@ -1107,6 +1151,55 @@ int ghx_uexchange_self(const ghx_exchange* ex, void* const* field_ptrs, int32_t 
         check_ptr(field_ptrs, "field_ptrs");
         check_ptr(buffers, "buffers");
         return ex->uself->execute_self(field_ptrs, n_fields, buffers, n_buffers, stream);
+    });
+}
+
+int ghx_uexchange_mixed_info(const ghx_exchange* ex, int32_t* mixed, int32_t* n_self_tiles,
+                             int32_t* n_peer_tiles)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(mixed, "mixed");
+        const uput_plan* p = ex->umixed.get();
+        *mixed = p ? 1 : 0;
+        if (n_self_tiles) *n_self_tiles = p ? int32_t(p->recs.size()) : 0;
+        if (n_peer_tiles) *n_peer_tiles = p ? int32_t(p->peer_recs.size()) : 0;
+        if (!p) set_error(ex->umixed_reason);
+        return GHX_OK;
+    });
+}
+
+namespace
+{
+// both launches of the index-list mixed form write / read one copy of each buffer
+void check_umixed(const ghx_exchange* ex)
+{
+    check_ptr(ex, "exchange");
+    if (!ex->umixed) throw invalid("index-list mixed exchange: " + ex->umixed_reason);
+    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
+        throw invalid("index-list mixed exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+}
+}  // namespace
+
+int ghx_uexchange_pack_self(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                            void* const* send_buffers, int32_t n_send, ghx_stream stream)
+{
+    return guarded([&] {
+        check_umixed(ex);
+        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
+        return ex->umixed->execute_self(field_ptrs, n_fields, send_buffers, n_send, stream);
+    });
+}
+
+int ghx_uexchange_unpack_peers(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                               void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
+{
+    return guarded([&] {
+        check_umixed(ex);
+        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
+        if (!ex->upunpack) return int(GHX_OK);  // the rank receives from no peer
+        return ex->upunpack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
     });
 }
 

@@ -472,6 +472,97 @@ void build_uself(exchange_plan& ex, int32_t me)
         refuse(e.what());
     }
 }
+
+// The mixed form of an exchange of unstructured items with self AND peer messages (make_umixed,
+// k_pack_self_u), built device-less with the exchange: the pack launch also stores the self
+// messages' halos, the unpack launch (ex.upunpack) covers the peer recv buffers only. A recv
+// buffer is a self message when it belongs to this rank and a send buffer of the same domain
+// pair, size and rank exists (build_mixed's match); its unpack entries pair with the pack entries
+// at the same (send buffer slot, buffer offset). Left absent, with the reason in
+// ex.umixed_reason, when the exchange has a structured item, no self or no peer message, entries
+// that do not pair, or what make_umixed refuses.
+void build_umixed(exchange_plan& ex, int32_t me)
+{
+    const std::vector<ghx_upack_entry>& sent = ex.uentries[0];
+    const std::vector<ghx_upack_entry>& rent = ex.uentries[1];
+    auto refuse = [&](const std::string& why) {
+        ex.umixed.reset();
+        ex.upunpack.reset();
+        ex.umixed_reason = "not mixed: " + why;
+    };
+    if (ex.spack || ex.sunpack || !ex.entries[0].empty() || !ex.entries[1].empty())
+        return refuse("the exchange has structured items");
+    std::vector<int> send_of_recv(ex.recv.size(), -1);
+    std::vector<char> self_send(ex.send.size(), 0);
+    bool any_self = false, any_peer = false;
+    for (size_t j = 0; j < ex.recv.size(); ++j)
+    {
+        const xbuffer& r = ex.recv[j];
+        any_peer = any_peer || r.rank != me;
+        if (r.rank != me) continue;
+        for (size_t i = 0; i < ex.send.size(); ++i)
+        {
+            const xbuffer& s = ex.send[i];
+            if (s.rank == me && !self_send[i] && s.first_id == r.first_id && s.second_id == r.second_id &&
+                s.size == r.size)
+            {
+                send_of_recv[j] = int(i);
+                self_send[i] = 1;
+                any_self = true;
+                break;
+            }
+        }
+    }
+    for (const xbuffer& s : ex.send) any_peer = any_peer || s.rank != me;
+    if (!any_self)
+        return refuse("the exchange has no self message (no recv buffer that is the send buffer of "
+                      "the same domain pair on this rank)");
+    if (!any_peer) return refuse("the exchange has no peer message (every buffer stays on this rank)");
+    std::map<std::pair<int32_t, uint64_t>, const ghx_upack_entry*> by_bytes;  // self pack entries
+    std::vector<ghx_upack_entry> src, dst, peers, peer_recv;
+    size_t n_self_pack = 0;
+    for (const ghx_upack_entry& e : sent)
+    {
+        if (!self_send[size_t(e.buffer_slot)])
+        {
+            peers.push_back(e);
+            continue;
+        }
+        by_bytes[{e.buffer_slot, e.buffer_offset}] = &e;
+        ++n_self_pack;
+    }
+    if (by_bytes.size() != n_self_pack)
+        return refuse("the self messages' pack and unpack entries do not pair one to one");
+    for (const ghx_upack_entry& r : rent)
+    {
+        const int i = send_of_recv[size_t(r.buffer_slot)];
+        if (i < 0)
+        {
+            peer_recv.push_back(r);
+            continue;
+        }
+        const auto it = by_bytes.find({i, r.buffer_offset});
+        if (it == by_bytes.end())
+            return refuse("an unpack entry of a self message has no pack entry at the same buffer bytes");
+        src.push_back(*it->second);
+        dst.push_back(r);
+        dst.back().buffer_slot = i;  // a self message's recv buffer IS its send buffer
+        by_bytes.erase(it);
+    }
+    if (!by_bytes.empty())
+        return refuse("the self messages' pack and unpack entries do not pair one to one");
+    try
+    {
+        ex.umixed = make_umixed(src.data(), dst.data(), int(src.size()), peers.data(), int(peers.size()));
+        if (!peer_recv.empty())
+            ex.upunpack = std::make_unique<uplan>(peer_recv.data(), int(peer_recv.size()), 1);
+        ex.umixed_reason.clear();
+    }
+    catch (const invalid& e)
+    {
+        refuse(e.what());
+    }
+}
 }  // namespace
 
 // The put plan of ghx_cs_put_create (cs_put_plan, k_put_cs): build_cs_self's pairing without the
@@ -649,6 +740,7 @@ std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, cons
     if (cs) build_cs_self(*ex, cs, items[0].pattern->my_rank, rhalos);
     else ex->cs_self_reason = "not fusable: not a cubed-sphere exchange";
     build_uself(*ex, items[0].pattern->my_rank);
+    build_umixed(*ex, items[0].pattern->my_rank);
     return ex;
 }
 

@@ -66,6 +66,13 @@ struct exchange_plan
     // this rank (ghx_uexchange_self, k_self_u): null when it cannot be fused, uself_reason says why
     std::unique_ptr<uput_plan> uself;
     std::string uself_reason;
+    // an exchange of unstructured items with self AND peer messages (ghx_uexchange_pack_self,
+    // k_pack_self_u): the pack plan that also completes the self messages, and the unpack plan of
+    // the peer messages alone (null: the rank receives from no peer). umixed is null when the
+    // form does not apply, umixed_reason then says why
+    std::unique_ptr<uput_plan> umixed;
+    std::unique_ptr<uplan> upunpack;
+    std::string umixed_reason;
 
     void make_split();  // the per-buffer plans (ghx_exchange_split)
 

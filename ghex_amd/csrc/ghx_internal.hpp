@@ -300,6 +300,20 @@ struct kargs_pcs
     uint64_t dst_ptr[GHX_MAX_SLOTS];
 };
 
+// Arguments of the index-list pack that also completes the self messages (k_pack_self_u): blocks
+// [0, n_self_tiles) take the seg_up record (with its buffer side, as k_self_u's) at their index,
+// the next n_peer_tiles a seg_u tile record of the peer messages' pack plan. Field slots of both
+// parts index field_ptr, buffer slots the send buffers in buf_ptr.
+struct kargs_um
+{
+    const void* self_recs;
+    const void* peer_recs;
+    uint32_t n_self_tiles;
+    uint32_t n_peer_tiles;
+    uint64_t field_ptr[GHX_MAX_SLOTS];
+    uint64_t buf_ptr[GHX_MAX_SLOTS];
+};
+
 // Double-buffered buffers (the direct exchange's one-launch epochs, ghx_epochs.hip): a buffer
 // exists twice, its odd-parity copy `offset` bytes after the even one, and a launch uses the copy
 // of the exchange's parity, read on the device from the epoch counter (so that a captured graph
@@ -341,6 +355,8 @@ int launch_put_u(const kargs& a, void* stream, uint32_t grid, bool runs);
 // tile_recs: seg_up records with their buffer side; field_ptr: the fields of both sides, buf_ptr:
 // the send buffers
 int launch_self_u(const kargs& a, void* stream, uint32_t grid, bool runs);
+// self_recs: seg_up records with their buffer side, peer_recs: seg_u tile records (pack)
+int launch_pack_self_u(const kargs_um& a, void* stream, uint32_t grid, bool runs);
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

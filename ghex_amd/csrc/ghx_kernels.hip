@@ -1618,6 +1618,71 @@ __global__ __launch_bounds__(kBlock) void k_self_u(kargs a)
     }
 }
 
+// Index-list pack that also completes the self messages (the mixed form of an exchange with self
+// AND peer list messages): blocks [0, n_self_tiles) take a seg_up record and run k_self_u's tile
+// (sending field -> send buffer and receiving field), the next n_peer_tiles a seg_u tile record of
+// the peer messages' pack plan and run k_copy<true, seg_u>'s (field -> send buffer). The planner
+// (make_umixed) guarantees that no peer tile loads a cell a self tile stores, so the two kinds
+// need no order. RUNS: every segment of BOTH parts takes its run path (uput_plan::execute_self
+// decides with the launch's pointers). Field slots of both parts at field_ptr, buffer slots at
+// buf_ptr.
+template<bool RUNS>
+__global__ __launch_bounds__(kBlock) void k_pack_self_u(kargs_um a)
+{
+    const seg_up* __restrict__ self = static_cast<const seg_up*>(a.self_recs);
+    const seg_u* __restrict__ peers = static_cast<const seg_u*>(a.peer_recs);
+    const uint32_t n_tiles = a.n_self_tiles + a.n_peer_tiles;
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x)
+    {
+        if (t < a.n_self_tiles)  // uniform per workgroup
+        {
+            const seg_up s = self[t];
+            const uint32_t start = s.first_tile * s.tile_bytes;
+            const uint32_t end = min(start + s.tile_bytes, s.bytes);
+            const char* src = reinterpret_cast<const char*>(a.field_ptr[s.src_slot]);
+            char* dst = reinterpret_cast<char*>(a.field_ptr[s.dst_slot]);
+            char* buf = reinterpret_cast<char*>(a.buf_ptr[s.buf_slot] + s.buf_off);
+            if constexpr (RUNS)
+            {
+                if (s.row_bytes == 8) self_runs<8>(s, src, dst, buf, start, end);
+                else self_runs<4>(s, src, dst, buf, start, end);
+            }
+            else
+            {
+                int w = s.wlog2;
+                w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(src)));
+                w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(dst)));
+                w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
+                if (s.src_lid64)
+                {
+                    if (s.dst_lid64) self_tile_u_w<true, true>(s, src, dst, buf, start, end, w);
+                    else self_tile_u_w<true, false>(s, src, dst, buf, start, end, w);
+                }
+                else if (s.dst_lid64) self_tile_u_w<false, true>(s, src, dst, buf, start, end, w);
+                else self_tile_u_w<false, false>(s, src, dst, buf, start, end, w);
+            }
+            continue;
+        }
+        const seg_u s = peers[t - a.n_self_tiles];
+        const uint32_t start = s.first_tile * s.tile_bytes;
+        const uint32_t end = min(start + s.tile_bytes, s.bytes);
+        char* field = reinterpret_cast<char*>(a.field_ptr[s.field_slot]);
+        char* buf = reinterpret_cast<char*>(a.buf_ptr[s.buf_slot]) + s.buf_off;
+        if constexpr (RUNS)
+        {
+            if (s.row_bytes == 8) copy_runs<true, 8>(s, field, buf, start, end);
+            else copy_runs<true, 4>(s, field, buf, start, end);
+        }
+        else
+        {
+            int w = s.wlog2;
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(field)));
+            w = min(w, ptr_wlog2(reinterpret_cast<uint64_t>(buf)));
+            copy_any<true, kU>(s, field, buf, start, end, w);
+        }
+    }
+}
+
 int launched(const char* what)
 {
     const hipError_t e = hipGetLastError();
@@ -1763,6 +1828,16 @@ int launch_self_u(const kargs& a, void* stream, uint32_t grid, bool runs)
     if (runs) launch(k_self_u<true>, grid, static_cast<hipStream_t>(stream), a);
     else launch(k_self_u<false>, grid, static_cast<hipStream_t>(stream), a);
     return launched("index-list self-exchange");
+}
+
+int launch_pack_self_u(const kargs_um& a, void* stream, uint32_t grid, bool runs)
+{
+    const uint32_t n_tiles = a.n_self_tiles + a.n_peer_tiles;
+    if (n_tiles == 0) return GHX_OK;
+    grid = min(grid, n_tiles);
+    if (runs) launch(k_pack_self_u<true>, grid, static_cast<hipStream_t>(stream), a);
+    else launch(k_pack_self_u<false>, grid, static_cast<hipStream_t>(stream), a);
+    return launched("index-list pack with self messages");
 }
 
 template<bool DBL, bool REC>

@@ -1359,27 +1359,53 @@ int uput_plan::execute(void* const* src, int ns, void* const* dst, int nd, void*
 // ---------------------------------------------------------------------------------------------
 int uput_plan::execute_self(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
 {
-    if (recs.empty()) return GHX_OK;
-    const int nfs = std::max(max_src_slot, max_dst_slot);
+    const uint32_t n_peer_tiles = uint32_t(peer_recs.size());
+    if (recs.empty() && n_peer_tiles == 0) return GHX_OK;
+    const int nfs = std::max(std::max(max_src_slot, max_dst_slot), peers ? peers->max_field_slot : -1);
     if (!fptr || !bptr || nf <= nfs || nb <= max_buf_slot)
         throw invalid("pointer arrays do not cover the plan's slots");
-    if (!dev.recs || !dev.lids) throw hip_error("plan has no device tables (no HIP device at creation)");
-    kargs a{};
-    a.tile_recs = dev.recs;
-    a.n_tiles = uint32_t(recs.size());
-    fill_slots(a.field_ptr, fptr, {}, nfs + 1, "field");
-    fill_slots(a.buf_ptr, bptr, {}, max_buf_slot + 1, "buffer");
+    if ((!recs.empty() && (!dev.recs || !dev.lids)) || (n_peer_tiles && !peer_dev.recs))
+        throw hip_error("plan has no device tables (no HIP device at creation)");
+    uint64_t field_ptr[GHX_MAX_SLOTS] = {}, buf_ptr[GHX_MAX_SLOTS] = {};
+    fill_slots(field_ptr, fptr, {}, nfs + 1, "field");
+    fill_slots(buf_ptr, bptr, {}, max_buf_slot + 1, "buffer");
     // the run-path kernel when every segment qualifies with these pointers: both fields aligned
     // to the row, every message chunk of the buffer 16-B aligned
     bool runs = run_ok;
     for (size_t k = 0; runs && k < segs.size(); ++k)
-        runs = a.field_ptr[segs[k].src_slot] % segs[k].row_bytes == 0 &&
-               a.field_ptr[segs[k].dst_slot] % segs[k].row_bytes == 0 &&
-               (a.buf_ptr[segs[k].buf_slot] + segs[k].buf_off) % 16 == 0;
-    return launch_self_u(a, stream, grid_for_tiles(a.n_tiles), runs);
+        runs = field_ptr[segs[k].src_slot] % segs[k].row_bytes == 0 &&
+               field_ptr[segs[k].dst_slot] % segs[k].row_bytes == 0 &&
+               (buf_ptr[segs[k].buf_slot] + segs[k].buf_off) % 16 == 0;
+    if (!peers)
+    {
+        kargs a{};
+        a.tile_recs = dev.recs;
+        a.n_tiles = uint32_t(recs.size());
+        std::copy(field_ptr, field_ptr + GHX_MAX_SLOTS, a.field_ptr);
+        std::copy(buf_ptr, buf_ptr + GHX_MAX_SLOTS, a.buf_ptr);
+        return launch_self_u(a, stream, grid_for_tiles(a.n_tiles), runs);
+    }
+    // the mixed form: the run variant only when the peer part qualifies too (uplan::execute's rule)
+    for (const seg_u& s : peers->groups[0].host_segs)
+        runs = runs && s.runs && s.tile_bytes % 16 == 0 && (buf_ptr[s.buf_slot] + s.buf_off) % 16 == 0 &&
+               field_ptr[s.field_slot] % s.row_bytes == 0;
+    kargs_um a{};
+    a.self_recs = dev.recs;
+    a.peer_recs = peer_dev.recs;
+    a.n_self_tiles = uint32_t(recs.size());
+    a.n_peer_tiles = n_peer_tiles;
+    std::copy(field_ptr, field_ptr + GHX_MAX_SLOTS, a.field_ptr);
+    std::copy(buf_ptr, buf_ptr + GHX_MAX_SLOTS, a.buf_ptr);
+    return launch_pack_self_u(a, stream, grid_for_tiles(a.n_self_tiles + a.n_peer_tiles), runs);
 }
 
-std::unique_ptr<uput_plan> make_uself(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n)
+namespace
+{
+// make_uself and make_umixed: the self messages' plan and every check that makes ONE launch equal
+// pack followed by unpack; with `peers`, the messages that leave the rank (packed by the same
+// launch) join the buffer-range check and the cell check.
+std::unique_ptr<uput_plan> plan_uself(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n,
+                                      const ghx_upack_entry* peers, int n_peers)
 {
     const size_t nk = n > 0 ? size_t(n) : 0;
     std::vector<ghx_uput_entry> se(nk), de(nk);
@@ -1399,19 +1425,56 @@ std::unique_ptr<uput_plan> make_uself(const ghx_upack_entry* src, const ghx_upac
         de[size_t(k)] = {d.data, d.field_slot, d.lids, d.n_lids};
         place[size_t(k)] = {s.buffer_slot, s.buffer_offset};
     }
+    for (int j = 0; j < n_peers; ++j)
+    {
+        if (peers[j].field_slot < 0 || peers[j].buffer_slot < 0) throw invalid("negative slot");
+        if (peers[j].field_slot >= GHX_MAX_SLOTS || peers[j].buffer_slot >= GHX_MAX_SLOTS)
+            throw invalid("a peer message's field or buffer slot is 64 or more (the pack with self "
+                          "messages is one launch, no launch groups)");
+    }
     // descriptors, lids and the agreement of the two sides: the put's checks
     auto p = std::make_unique<uput_plan>(se.data(), de.data(), n, place.data());
-    // no two messages share buffer bytes
-    std::vector<std::pair<std::pair<int32_t, uint64_t>, uint64_t>> ranges;  // (slot, first), end
-    for (int k = 0; k < n; ++k)
+    // the peer messages: descriptors and lids by the pack plan's checks, its segments and tiles
+    if (peers)
     {
-        const uint64_t nb = uint64_t(src[k].n_lids) * uint64_t(src[k].data.levels) * uint64_t(src[k].data.elem_size);
-        if (nb) ranges.push_back({{src[k].buffer_slot, src[k].buffer_offset}, src[k].buffer_offset + nb});
+        p->peers = std::make_unique<uplan>(peers, n_peers, 0);
+        p->max_buf_slot = std::max(p->max_buf_slot, p->peers->max_buf_slot);
+        const launch_group<seg_u>& g = p->peers->groups[0];  // slots < 64: one group, identity maps
+        for (size_t t = 0; t < g.n_tiles; ++t)
+        {
+            p->peer_recs.push_back(g.host_segs[g.host_tiles[2 * t]]);
+            p->peer_recs.back().first_tile = g.host_tiles[2 * t + 1];
+        }
+        if (!p->peer_recs.empty() && have_device())
+        {
+            const size_t rb = p->peer_recs.size() * sizeof(seg_u);
+            if (hipMalloc(&p->peer_dev.recs, rb) != hipSuccess) throw hip_error("hipMalloc(peer tile records)");
+            if (hipMemcpy(p->peer_dev.recs, p->peer_recs.data(), rb, hipMemcpyHostToDevice) != hipSuccess)
+                throw hip_error("hipMemcpy(peer tile records)");
+        }
     }
-    std::sort(ranges.begin(), ranges.end());
+    // no two messages share buffer bytes
+    struct range
+    {
+        int32_t slot;
+        uint64_t first, end;
+        bool peer;
+    };
+    std::vector<range> ranges;
+    auto add_range = [&](const ghx_upack_entry& e, bool peer) {
+        const uint64_t nb = uint64_t(e.n_lids) * uint64_t(e.data.levels) * uint64_t(e.data.elem_size);
+        if (nb) ranges.push_back({e.buffer_slot, e.buffer_offset, e.buffer_offset + nb, peer});
+    };
+    for (int k = 0; k < n; ++k) add_range(src[k], false);
+    for (int j = 0; j < n_peers; ++j) add_range(peers[j], true);
+    std::sort(ranges.begin(), ranges.end(), [](const range& a, const range& b) {
+        return std::make_pair(a.slot, a.first) < std::make_pair(b.slot, b.first);
+    });
     for (size_t i = 1; i < ranges.size(); ++i)
-        if (ranges[i].first.first == ranges[i - 1].first.first && ranges[i].first.second < ranges[i - 1].second)
-            throw invalid("two messages overlap in one buffer");
+        if (ranges[i].slot == ranges[i - 1].slot && ranges[i].first < ranges[i - 1].end)
+            throw invalid(ranges[i].peer || ranges[i - 1].peer
+                              ? "a peer message overlaps another message in one buffer"
+                              : "two messages overlap in one buffer");
     // A fused launch reads and writes in no defined order: it equals pack followed by unpack only
     // if no cell (field slot, lid) is read and written, and none is written twice.
     std::vector<std::pair<int32_t, int64_t>> reads, writes;
@@ -1428,7 +1491,30 @@ std::unique_ptr<uput_plan> make_uself(const ghx_upack_entry* src, const ghx_upac
         if (std::binary_search(writes.begin(), writes.end(), c))
             throw invalid("a cell of a field slot is both a source and a target of the plan (the "
                           "launch's loads and stores have no order)");
+    // the hazard rule of the mixed form: in the two-launch path every pack load precedes every
+    // unpack store; here a peer tile may load a cell after a self tile has stored it
+    for (int j = 0; j < n_peers; ++j)
+        for (int64_t i = 0; i < peers[j].n_lids; ++i)
+            if (std::binary_search(writes.begin(), writes.end(), std::make_pair(peers[j].field_slot, peers[j].lids[i])))
+                throw invalid("a target cell of a self message is a source cell of a peer message "
+                              "(the launch's loads and stores have no order)");
     return p;
+}
+}  // namespace
+
+std::unique_ptr<uput_plan> make_uself(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n)
+{
+    return plan_uself(src, dst, n, nullptr, 0);
+}
+
+std::unique_ptr<uput_plan> make_umixed(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n_self,
+                                       const ghx_upack_entry* peers, int n_peers)
+{
+    if (n_self < 1 || !src || !dst)
+        throw invalid("no self message (an exchange of peer messages alone is ghx_uplan_create's)");
+    if (n_peers < 1 || !peers)
+        throw invalid("no peer message (an exchange of self messages alone is ghx_uself_create's)");
+    return plan_uself(src, dst, n_self, peers, n_peers);
 }
 
 }  // namespace ghx

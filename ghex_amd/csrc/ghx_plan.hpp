@@ -247,6 +247,12 @@ struct uput_plan
     uput_plan(const ghx_uput_entry* src, const ghx_uput_entry* dst, int n,
               const ubuf_place* buf = nullptr);
     int execute(void* const* src, int ns, void* const* dst, int nd, void* stream) const;
+    // The mixed form (make_umixed, k_pack_self_u): the pack plan of the messages that leave the
+    // rank, one launch group with the caller's slots, and its tile records in dispatch order
+    // (kept whatever g_tune.tile_records says). The launch runs them after the self tiles.
+    std::unique_ptr<uplan> peers;
+    std::vector<seg_u> peer_recs;
+    device_tables peer_dev;        // recs: peer_recs
     // a plan with a buffer side: fields (both sides' slots) and send buffers, ONE launch
     int execute_self(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
@@ -254,6 +260,12 @@ struct uput_plan
 // message bytes. Throws `invalid` with the reason for what one fused launch cannot serve or would
 // not do exactly as pack followed by unpack does (see include/ghx.h).
 std::unique_ptr<uput_plan> make_uself(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n);
+// The plan of ghx_umixed_create: make_uself's plan of the self messages with the pack plan of
+// `peers` (the plan a uplan of direction 0 makes of them) for the same launch. Refuses, beyond
+// make_uself's reasons, a peer message that shares buffer bytes with another message and a peer
+// source cell that a self message writes: the launch then equals pack followed by unpack.
+std::unique_ptr<uput_plan> make_umixed(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n_self,
+                                       const ghx_upack_entry* peers, int n_peers);
 
 // The per-call entry points' plans, cached by content (ghx_cache.cpp): the plan of the call's
 // descriptor and spaces, or index list, is built on first use and executed on `stream`.

@@ -12,7 +12,11 @@ from .pattern import PatternContainer
 
 def make_communication_object(context, fuse_lists: bool = False, **options) -> CommunicationObject:
     """fuse_lists: when every message of an exchange stays on this rank, pack and unpack run as
-    ONE launch (ghx_uexchange_self); an exchange that cannot be fused takes the usual path."""
+    ONE launch (ghx_uexchange_self); an exchange that cannot be fused takes the usual path.
+    fuse_lists_mixed (through **options): when an exchange has self AND peer messages, the pack
+    launch also writes the self messages' halos and the unpack launch covers the peer messages
+    only (ghx_uexchange_pack_self, ghx_uexchange_unpack_peers); an exchange without that form
+    takes the usual path. Both are off by default."""
     return CommunicationObject(context, fuse_lists=fuse_lists, **options)
 
 

@@ -801,6 +801,43 @@ typedef struct ghx_uself_segment_info
 int ghx_uself_segment(const ghx_uself* p, int32_t k, ghx_uself_segment_info* out);
 int ghx_uself_destroy(ghx_uself* p);
 
+/* The mixed form of the plan above: a pack of index-list messages that also completes those that
+ * stay on the rank (no reference counterpart, as above). src[k] / dst[k], k < n_self, are the pack
+ * and the unpack entry of one self message (ghx_uself_create's contract); peers[j], j < n_peers,
+ * are pack entries of messages that leave the rank (pack only). The field slots of all three
+ * arrays index ONE field pointer array, the buffer slots the send buffers. The result is an
+ * ordinary ghx_uself: ghx_uself_execute runs ONE launch (k_pack_self_u) that does for the self
+ * messages what ghx_uself_create's launch does and packs the peer messages as a ghx_uplan pack of
+ * `peers` does — byte for byte what a ghx_uplan pack of every entry followed by a ghx_uplan unpack
+ * of dst leaves in the buffers and the fields. ghx_uself_info reports bytes, segments and tiles of
+ * both parts, ghx_uself_segment describes the self segments, ghx_umixed_peer_segment the peer
+ * ones, ghx_uself_destroy frees it. The self part is exactly ghx_uself_create's plan (rows,
+ * tiles, refusals); the peer part has exactly the segments and tiles of
+ * ghx_uplan_create(peers, n_peers, 0): the same wlog2, mode, tiles and split below 2^30 bytes, in
+ * one launch group. The launch takes the 16-byte run path (knob "urun") only when every segment of
+ * both parts qualifies with the launch's pointers; a message moves the same bytes either way.
+ * Created without a device. GHX_ERR_INVALID, with the reason in ghx_last_error(), for every
+ * reason of ghx_uself_create and when: n_self < 1 or n_peers < 1 (an all-self plan is
+ * ghx_uself_create's, an all-peer one ghx_uplan_create's); a field or buffer slot of a peer entry
+ * is negative or >= 64; a peer entry's byte range overlaps another message's, self or peer, in
+ * one buffer; a cell (field slot, lid) that a self message writes is a source cell of a peer
+ * entry. The last is the hazard rule: the two-launch exchange loads every pack source before it
+ * stores any unpack target, one launch orders nothing, so the check is what makes them equal;
+ * patterns always pass it (send lists hold inner cells, receive lists outer cells). The same lid
+ * on another field slot is another cell; cells are compared as (field slot, lid), so entries that
+ * describe one field slot with different layouts stay the caller's contract, as two slots given
+ * the same pointer do. */
+int ghx_umixed_create(const ghx_upack_entry* src, const ghx_upack_entry* dst, int32_t n_self,
+                      const ghx_upack_entry* peers, int32_t n_peers, ghx_uself** out);
+/* workgroup tiles of the self part, segments and tiles of the peer part; a plan of
+ * ghx_uself_create reports its tiles as self tiles and zeros for the peer part */
+int ghx_umixed_info(const ghx_uself* p, int32_t* n_self_tiles, int32_t* n_peer_segments,
+                    int32_t* n_peer_tiles);
+/* Peer segment k of a plan of ghx_umixed_create (host only), as ghx_uplan_segment describes the
+ * segments of the pack plan of `peers`. GHX_ERR_INVALID for k out of range or a plan without a
+ * peer part. */
+int ghx_umixed_peer_segment(const ghx_uself* p, int32_t k, ghx_usegment_info* out);
+
 /* The fused self exchange of an exchange of unstructured items. ghx_exchange_create also plans
  * ONE launch (a ghx_uself over the exchange's pack and unpack entries, paired by buffer slot and
  * buffer offset) when the exchange has unstructured items only and at least one message, every
@@ -816,6 +853,33 @@ int ghx_uexchange_self_info(const ghx_exchange* ex, int32_t* fusable, int32_t* n
                             int32_t* n_tiles);
 int ghx_uexchange_self(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                        void* const* buffers, int32_t n_buffers, ghx_stream stream);
+
+/* The mixed form of an exchange of unstructured items with self AND peer messages — the index-list
+ * counterpart of ghx_exchange_mixed / ghx_exchange_pack_self / ghx_exchange_unpack_peers; the
+ * reference's own test geometry (unstructured_test_case.hpp: four domains over two ranks) is such
+ * an exchange. ghx_exchange_create also plans it (a ghx_umixed_create plan and the unpack plan of
+ * the peer recv buffers) when: the exchange has unstructured items only; at least one recv buffer
+ * is a self message (it belongs to this rank and a send buffer of the same domain pair, size and
+ * rank exists); at least one send buffer goes to, or one recv buffer comes from, another rank;
+ * the self messages' unpack entries pair one to one with pack entries at the same (send buffer
+ * slot, buffer offset); and ghx_umixed_create's conditions hold (at most 64 items and 64 send
+ * buffers among them). ghx_uexchange_mixed_info works without a device; with *mixed = 0,
+ * ghx_last_error() holds the reason. ghx_uexchange_pack_self has ghx_exchange_pack's argument
+ * contract: ONE launch packs every send buffer and writes the self messages' halos.
+ * ghx_uexchange_unpack_peers has ghx_exchange_unpack's: it unpacks the peer recv buffers only,
+ * addressed by the caller's recv buffer indices, and enqueues nothing when the rank receives from
+ * no peer. Together they leave byte for byte what ghx_exchange_pack + ghx_exchange_unpack leave
+ * in fields and send buffers (a self message's recv buffer being its send buffer); pad bytes are
+ * not written. Both fail with GHX_ERR_INVALID on an exchange that is not mixed, or while either
+ * direction has parity set (ghx_exchange_set_parity): the direct exchange stays on its launches.
+ * ghx_exchange_mixed, ghx_exchange_self_fusable, ghx_uexchange_self_info and ghx_cs_self_info are
+ * unchanged by it. */
+int ghx_uexchange_mixed_info(const ghx_exchange* ex, int32_t* mixed, int32_t* n_self_tiles,
+                             int32_t* n_peer_tiles);
+int ghx_uexchange_pack_self(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                            void* const* send_buffers, int32_t n_send, ghx_stream stream);
+int ghx_uexchange_unpack_peers(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                               void* const* recv_buffers, int32_t n_recv, ghx_stream stream);
 
 /* Device-side access epochs of the zero-copy exchanges (bulk puts, direct pack): the reference's
  * access guards (include/ghex/rma/access_guard.hpp:35-140; per range: start/end_target_epoch on
