@@ -78,6 +78,15 @@ class USelfSegmentInfo(ctypes.Structure):
     _fields_ = UPutSegmentInfo._fields_ + [("buf_slot", c_i32), ("buf_off", c_u64)]
 
 
+class UAccumDestInfo(ctypes.Structure):
+    _fields_ = [("field_slot", c_i32), ("zero", c_i32), ("lid", c_i64), ("first", c_i64),
+                ("count", c_i64)]
+
+
+# element type codes of the adjoint accumulate (GHX_DT_*, include/ghx.h)
+DT_F32, DT_F64, DT_I32, DT_I64 = 1, 2, 3, 4
+
+
 class RegularDomain(ctypes.Structure):
     _fields_ = [("id", c_i32), ("rank", c_i32), ("first", c_i32 * 3), ("last", c_i32 * 3)]
 
@@ -145,6 +154,16 @@ _SIGS = {
     "ghx_uexchange_mixed_info": (c_i32, [c_vp, P(c_i32), P(c_i32), P(c_i32)]),
     "ghx_uexchange_pack_self": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_uexchange_unpack_peers": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_uaccum_create": (c_i32, [P(UPackEntry), P(c_i32), c_i32, P(UPackEntry), c_i32, P(c_vp)]),
+    "ghx_uaccum_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
+    "ghx_uaccum_info": (c_i32, [c_vp, P(c_u64), P(c_i64), P(c_i64), P(c_i64), P(c_i64), P(c_i32)]),
+    "ghx_uaccum_dest": (c_i32, [c_vp, c_i64, P(UAccumDestInfo)]),
+    "ghx_uaccum_contrib": (c_i32, [c_vp, c_i64, P(c_i32), P(c_i64)]),
+    "ghx_uaccum_destroy": (c_i32, [c_vp]),
+    "ghx_uexchange_adjoint_create": (c_i32, [c_vp, P(c_i32), c_i32]),
+    "ghx_uexchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64)]),
+    "ghx_uexchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_uexchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
                               c_i32, c_vp]),
     "ghx_udomain_create": (c_i32, [c_i32, P(c_i64), c_i64, P(c_i64), c_i64, P(c_vp)]),

@@ -565,9 +565,106 @@ class CommunicationObject:
             ev = self._done_event(stream)
         return CommunicationHandle(self, stream, ev)
 
-    def _host_buffers(self, plan, sends, recvs):
+    # -- adjoint exchange ------------------------------------------------------------------------
+    def _adjoint_plan(self, bis):
+        """The plan of `bis` with its adjoint plans attached (built on first use): the reverse
+        pack and the accumulate (ghx_uexchange_adjoint_create, k_accum_u)."""
+        if self.direct or self.pipelined:
+            raise ValueError("the adjoint exchange is the plain communication object's "
+                             "(no direct=True, no pipelined=True)")
+        for bi in bis:
+            if bi.field.kind != 1 or getattr(bi.field, "cs_item", None) is not None:
+                raise ValueError("the adjoint exchange takes unstructured fields only (structured "
+                                 "and cubed-sphere send boxes overlap)")
+        codes = [bi.field.dtype_code() for bi in bis]  # TypeError for any other dtype
+        plan = self.plan(bis)
+        if getattr(plan, "_adjoint_codes", None) != codes:
+            _ghx.call("ghx_uexchange_adjoint_create", plan.h, _ghx.i32_array(codes), len(codes))
+            plan._adjoint_codes = codes
+        return plan
+
+    def adjoint_exchange(self, *buffer_infos, zero_halos: bool = True) -> CommunicationHandle:
+        """The transpose of exchange() for unstructured fields, non-blocking on the current
+        stream: every halo cell's value is sent back to the cell's owner and added to it, in a
+        fixed order (bitwise reproducible, no atomics); with zero_halos the halo cells are then
+        set to zero (the true transpose), without it they keep their values (assembly). The plain
+        path: reverse pack into the receive buffers, the forward transport with the roles
+        swapped, accumulate from the send buffers."""
         import torch
-        key = id(plan)
+        bis = self._as_list(buffer_infos)
+        stream = torch.cuda.current_stream(bis[0].field.device.index) if bis else None
+        return self._start_adjoint(bis, stream, zero_halos)
+
+    def schedule_adjoint_exchange(self, stream, *buffer_infos,
+                                  zero_halos: bool = True) -> CommunicationHandle:
+        """adjoint_exchange after all work submitted to `stream` (None = the current stream), as
+        schedule_exchange schedules exchange()."""
+        bis = self._as_list(buffer_infos)
+        if bis:
+            stream = as_stream(stream, bis[0].field.device)
+        return self._start_adjoint(bis, stream, zero_halos)
+
+    def _start_adjoint(self, bis, stream, zero_halos) -> CommunicationHandle:
+        import torch
+        self.complete_schedule_exchange()
+        if self._valid:
+            raise RuntimeError("earlier exchange operation was not finished")
+        if not bis:
+            return CommunicationHandle(None, None, None)
+        plan = self._adjoint_plan(bis)
+        send, recv = self.buffers(plan, bis[0].field.device)
+        fptrs = _ghx.ptr_array([bi.field.data_ptr() for bi in bis])
+        sptrs = _ghx.ptr_array([t.data_ptr() for t in send])
+        rptrs = _ghx.ptr_array([t.data_ptr() for t in recv])
+        with torch.cuda.stream(stream):
+            _ghx.call("ghx_uexchange_adjoint_pack", plan.h, fptrs, len(bis), rptrs, len(recv),
+                      stream.cuda_stream)
+            # the forward transport with the roles swapped: peer receive buffers are sent, peer
+            # send buffers receive; tags as they are. A self message's receive buffer is its
+            # send buffer: no transport
+            me = self.context.rank()
+            sends = [(x["rank"], x["tag"], recv[i][:x["size"]])
+                     for i, x in enumerate(plan.recv) if x["rank"] != me]
+            recvs = [(x["rank"], x["tag"], send[i][:x["size"]])
+                     for i, x in enumerate(plan.send) if x["rank"] != me]
+            if self.staging == "host":
+                self._exchange_host_staged(plan, sends, recvs, stream, key=("adjoint", id(plan)))
+            else:
+                for w in route(self.context, sends, recvs):
+                    w.wait()
+            _ghx.call("ghx_uexchange_adjoint_accumulate", plan.h, fptrs, len(bis), sptrs,
+                      len(send), 1 if zero_halos else 0, stream.cuda_stream)
+            ev = self._done_event(stream)
+        self._valid = True
+        return CommunicationHandle(self, stream, ev)
+
+    def adjoint_pack_only(self, bis, stream=None):
+        """The adjoint's first launch alone: gather the halo cells into the receive buffers."""
+        import torch
+        plan = self._adjoint_plan(bis)
+        send, recv = self.buffers(plan, bis[0].field.device)
+        s = (stream or torch.cuda.current_stream()).cuda_stream
+        _ghx.call("ghx_uexchange_adjoint_pack", plan.h,
+                  _ghx.ptr_array([b.field.data_ptr() for b in bis]), len(bis),
+                  _ghx.ptr_array([t.data_ptr() for t in recv]), len(recv), s)
+        return plan, send, recv
+
+    def adjoint_accumulate_only(self, bis, zero_halos: bool = True, stream=None):
+        """The adjoint's second launch alone: add the send buffers' contributions to their owner
+        cells and, with zero_halos, zero the halo cells."""
+        import torch
+        plan = self._adjoint_plan(bis)
+        send, recv = self.buffers(plan, bis[0].field.device)
+        s = (stream or torch.cuda.current_stream()).cuda_stream
+        _ghx.call("ghx_uexchange_adjoint_accumulate", plan.h,
+                  _ghx.ptr_array([b.field.data_ptr() for b in bis]), len(bis),
+                  _ghx.ptr_array([t.data_ptr() for t in send]), len(send),
+                  1 if zero_halos else 0, s)
+        return plan, send, recv
+
+    def _host_buffers(self, plan, sends, recvs, key=None):
+        import torch
+        key = id(plan) if key is None else key
         h = self._host.get(key)
         if h is None:
             h = ([torch.empty(t.numel(), dtype=torch.uint8, pin_memory=True) for _, _, t in sends],
@@ -575,14 +672,14 @@ class CommunicationObject:
             self._host[key] = h
         return h
 
-    def _exchange_host_staged(self, plan, sends, recvs, stream):
+    def _exchange_host_staged(self, plan, sends, recvs, stream, key=None):
         """pack (queued) -> D2H per buffer -> host sends as copies land; host recvs -> H2D per
         buffer as messages land; the caller queues the unpack afterwards. copy_engine="probe":
         copies on the measured SDMA engines (the host waits for the pack, the copy engines run
         D2H and H2D concurrently; the unpack is queued behind an L2 acquire); "runtime": the
         copies are hipMemcpyAsync on the exchange stream."""
         import torch
-        hs, hr = self._host_buffers(plan, sends, recvs)
+        hs, hr = self._host_buffers(plan, sends, recvs, key)  # key: the adjoint's own buffers
         dist = self.context.distributed
         group = self._host_group
         gr = self.context.global_rank

@@ -1203,6 +1203,138 @@ int ghx_uexchange_unpack_peers(const ghx_exchange* ex, void* const* field_ptrs, 
     });
 }
 
+int ghx_uaccum_create(const ghx_upack_entry* contrib, const int32_t* dtypes, int32_t n,
+                      const ghx_upack_entry* zero, int32_t n_zero, ghx_uaccum** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        *out = nullptr;
+        if (n < 0 || n_zero < 0 || (n && (!contrib || !dtypes)) || (n_zero && !zero))
+            throw invalid("bad entry arrays");
+        *out = new ghx_uaccum(contrib, dtypes, n, zero, n_zero);
+        return GHX_OK;
+    });
+}
+
+int ghx_uaccum_execute(const ghx_uaccum* p, void* const* field_ptrs, int32_t n_fields,
+                       void* const* buffer_ptrs, int32_t n_buffers, int32_t zero_halos,
+                       ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        return p->execute(field_ptrs, n_fields, buffer_ptrs, n_buffers, zero_halos != 0, stream);
+    });
+}
+
+int ghx_uaccum_info(const ghx_uaccum* p, uint64_t* bytes, int64_t* n_dest, int64_t* n_zero_dest,
+                    int64_t* n_contrib, int64_t* max_per_dest, int32_t* n_tiles)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (bytes) *bytes = p->bytes;
+        if (n_dest) *n_dest = int64_t(p->n_dest);
+        if (n_zero_dest) *n_zero_dest = int64_t(p->n_zero_dest);
+        if (n_contrib) *n_contrib = int64_t(p->contribs.size());
+        if (max_per_dest) *max_per_dest = p->max_per_dest;
+        if (n_tiles) *n_tiles = int32_t(p->tiles.size());
+        return GHX_OK;
+    });
+}
+
+int ghx_uaccum_dest(const ghx_uaccum* p, int64_t k, ghx_uaccum_dest_info* out)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        check_ptr(out, "out");
+        if (k < 0 || uint64_t(k) >= p->n_dest + p->n_zero_dest) throw invalid("destination index out of range");
+        const bool zero = uint64_t(k) >= p->n_dest;
+        *out = ghx_uaccum_dest_info{};
+        out->field_slot = p->dest_slot[size_t(k)];
+        out->zero = zero ? 1 : 0;
+        out->lid = p->dest_lid[size_t(k)];
+        out->first = zero ? 0 : int64_t(p->ranges[size_t(k)].first);
+        out->count = zero ? 0 : int64_t(p->ranges[size_t(k)].count);
+        return GHX_OK;
+    });
+}
+
+int ghx_uaccum_contrib(const ghx_uaccum* p, int64_t j, int32_t* entry, int64_t* pos)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (j < 0 || uint64_t(j) >= p->contribs.size()) throw invalid("record index out of range");
+        if (entry) *entry = int32_t(p->contribs[size_t(j)].entry);
+        if (pos) *pos = int64_t(p->contribs[size_t(j)].pos);
+        return GHX_OK;
+    });
+}
+
+int ghx_uaccum_destroy(ghx_uaccum* p)
+{
+    return guarded([&] {
+        delete p;
+        return GHX_OK;
+    });
+}
+
+int ghx_uexchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        ex->make_adjoint(dtypes, n_items);
+        return GHX_OK;
+    });
+}
+
+int ghx_uexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_dest,
+                               int64_t* n_contrib)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(ready, "ready");
+        const uaccum_plan* p = ex->adj_accum.get();
+        *ready = p ? 1 : 0;
+        if (n_dest) *n_dest = p ? int64_t(p->n_dest) : 0;
+        if (n_contrib) *n_contrib = p ? int64_t(p->contribs.size()) : 0;
+        return GHX_OK;
+    });
+}
+
+namespace
+{
+// both launches of the adjoint use one copy of each buffer
+void check_adjoint(const ghx_exchange* ex)
+{
+    check_ptr(ex, "exchange");
+    if (!ex->adj_accum || !ex->adj_pack)
+        throw invalid("adjoint exchange: no adjoint plans (ghx_uexchange_adjoint_create)");
+    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+}
+}  // namespace
+
+int ghx_uexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                               void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
+{
+    return guarded([&] {
+        check_adjoint(ex);
+        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
+        return ex->adj_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+    });
+}
+
+int ghx_uexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
+                                     int32_t n_fields, void* const* send_buffers, int32_t n_send,
+                                     int32_t zero_halos, ghx_stream stream)
+{
+    return guarded([&] {
+        check_adjoint(ex);
+        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
+        return ex->adj_accum->execute(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
+    });
+}
+
 int ghx_uput_segment(const ghx_put* put, int32_t k, ghx_uput_segment_info* out)
 {
     return guarded([&] {

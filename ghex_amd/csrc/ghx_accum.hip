@@ -1,0 +1,179 @@
+// ghx_accum.hip — gfx950 (CDNA4) adjoint accumulate for index-list halos (k_accum_u).
+//
+// The adjoint of the halo exchange sends every halo copy of a cell back to the cell's owner and
+// sums it there. The contributions are already stored once: they are the message bytes a reverse
+// pack (a ghx_uplan of direction 0 over the receive lists) left in the buffers. This kernel is the
+// second pass: it sums per destination cell through an inverted index (uaccum_plan, ghx_accum_plan.cpp)
+// whose lists keep a fixed order, so the result is bitwise reproducible. No atomics, no LDS.
+//
+// A workgroup takes one tile of destination rows of one field slot, a lane one element
+// (destination d, level l): adjacent lanes take adjacent levels when a row's levels are adjacent
+// in the field, adjacent destinations otherwise. The lane loads the destination's record range and
+// lid, loads the cell, adds the contributions in record order — (entry, position) ascending — and
+// stores the cell once. The loads of up to kAccBatch contributions are issued together (indices
+// past the end clamped to the last record, their values not added), the adds stay in order: a
+// destination of a real pattern has a handful of contributions (one per domain that holds the cell
+// in its halo), so one trip serves it and no load waits for an earlier contribution's. A
+// destination with ONE contribution, the most common, takes one load of each table and no clamped
+// copies: the launch is bound by the load requests it issues (the duplicates cost 41 us of 203 at
+// levels = 8), not by the latency of a lane's chain. Arithmetic
+// is in the element type, integers as unsigned (they wrap). Zero tiles store zero bytes to their
+// rows and load nothing from the field. All address arithmetic is 64-bit.
+//
+// This is the one file of the library that knows an element type. It is compiled without
+// fast-math; the pragma below also keeps the compiler from contracting or reassociating.
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "ghx_addr.hpp"
+#include "ghx_internal.hpp"
+
+#pragma clang fp contract(off) reassociate(off)
+
+namespace ghx
+{
+// the calling thread's launch timing (ghx_kernels.hip, ghx_launch_timing)
+extern thread_local std::vector<std::pair<hipEvent_t, hipEvent_t>>* t_timing;
+
+namespace
+{
+#define GHX_GLOBAL __attribute__((address_space(1)))
+
+constexpr int kAccBatch = 4;  // contribution loads in flight per lane per trip
+
+// table records are loaded as vectors of their words (one global_load each)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template<typename T>
+__device__ __forceinline__ T load_contrib(const kargs_ua& a, uint32_t j, uint32_t l)
+{
+    const u32x2 c = ((const GHX_GLOBAL u32x2*)a.contribs)[j];  // entry, pos
+    const GHX_GLOBAL u32x4* ep = (const GHX_GLOBAL u32x4*)(a.entries + c.x);
+    const u32x4 e0 = ep[0];  // buf_off (2 words), n, levels
+    const u32x4 e1 = ep[1];  // levels_first, buf_slot, pos_stride, lev_stride
+    const uint64_t buf_off = uint64_t(e0.x) | (uint64_t(e0.y) << 32);
+    const uint64_t elem = uint64_t(c.y) * e1.z + uint64_t(l) * e1.w;
+    const char* p = reinterpret_cast<const char*>(a.buf_ptr[e1.y]) + buf_off + elem * sizeof(T);
+    return *(const GHX_GLOBAL T*)(p);
+}
+
+// element e of a tile -> (row, level)
+__device__ __forceinline__ void tile_element(const acc_tile& s, uint32_t e, uint32_t& r, uint32_t& l)
+{
+    if (s.lcontig)
+    {
+        r = fastdiv(e, s.mag);
+        l = e - r * s.levels;
+    }
+    else
+    {
+        l = fastdiv(e, s.mag);
+        r = e - l * s.n_rows;
+    }
+}
+
+__device__ __forceinline__ int64_t dest_lid(const kargs_ua& a, uint32_t d)
+{
+    if (a.lid64) return ((const GHX_GLOBAL int64_t*)a.lids)[d];
+    return ((const GHX_GLOBAL int32_t*)a.lids)[d];
+}
+
+template<typename T>
+__device__ __forceinline__ void accum_tile(const kargs_ua& a, const acc_tile& s)
+{
+    char* field = reinterpret_cast<char*>(a.field_ptr[s.field_slot]);
+    const uint32_t ne = s.n_rows * s.levels;  // < 2^32 (planner)
+    for (uint32_t e = threadIdx.x; e < ne; e += kBlock)
+    {
+        uint32_t r, l;
+        tile_element(s, e, r, l);
+        const uint32_t d = s.first_dest + r;
+        const u32x2 rg = ((const GHX_GLOBAL u32x2*)a.ranges)[d];  // first, count
+        const int64_t lid = dest_lid(a, d);
+        GHX_GLOBAL T* cell = (GHX_GLOBAL T*)(field + lid * s.index_stride_b + int64_t(l) * s.level_stride_b);
+        T acc = *cell;
+        uint32_t j = rg.x, left = rg.y;
+        if (left == 1)  // a cell with one halo copy, the common one: no clamped loads beside it
+        {
+            acc = T(acc + load_contrib<T>(a, j, l));
+            left = 0;
+        }
+        while (left)
+        {
+            T v[kAccBatch];
+#pragma unroll
+            for (uint32_t k = 0; k < kAccBatch; ++k) v[k] = load_contrib<T>(a, j + min(k, left - 1), l);
+#pragma unroll
+            for (uint32_t k = 0; k < kAccBatch; ++k) acc = k < left ? T(acc + v[k]) : acc;
+            const uint32_t step = min(uint32_t(kAccBatch), left);
+            j += step;
+            left -= step;
+        }
+        *cell = acc;
+    }
+}
+
+template<typename T>
+__device__ __forceinline__ void zero_tile(const kargs_ua& a, const acc_tile& s)
+{
+    char* field = reinterpret_cast<char*>(a.field_ptr[s.field_slot]);
+    const uint32_t ne = s.n_rows * s.levels;
+    for (uint32_t e = threadIdx.x; e < ne; e += kBlock)
+    {
+        uint32_t r, l;
+        tile_element(s, e, r, l);
+        const int64_t lid = dest_lid(a, s.first_dest + r);
+        *(GHX_GLOBAL T*)(field + lid * s.index_stride_b + int64_t(l) * s.level_stride_b) = T(0);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_accum_u(kargs_ua a)
+{
+    for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x)
+    {
+        const acc_tile s = a.tiles[t];
+        const bool wide = s.dtype == GHX_DT_F64 || s.dtype == GHX_DT_I64;
+        if (s.zero)
+        {
+            if (wide) zero_tile<uint64_t>(a, s);
+            else zero_tile<uint32_t>(a, s);
+        }
+        else if (s.dtype == GHX_DT_F32) accum_tile<float>(a, s);
+        else if (s.dtype == GHX_DT_F64) accum_tile<double>(a, s);
+        else if (wide) accum_tile<uint64_t>(a, s);
+        else accum_tile<uint32_t>(a, s);
+    }
+}
+}  // namespace
+
+int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid)
+{
+    if (a.n_tiles == 0) return GHX_OK;
+    grid = grid < a.n_tiles ? grid : a.n_tiles;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (t_timing && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
+    {
+        hipExtLaunchKernelGGL(k_accum_u, dim3(grid), dim3(kBlock), 0, s, e0, e1, 0, a);
+        t_timing->emplace_back(e0, e1);
+    }
+    else
+    {
+        if (e0) (void)hipEventDestroy(e0);
+        hipLaunchKernelGGL(k_accum_u, dim3(grid), dim3(kBlock), 0, s, a);
+    }
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess)
+    {
+        set_error(std::string("adjoint accumulate kernel launch failed: ") + hipGetErrorString(err));
+        return GHX_ERR_HIP;
+    }
+    return GHX_OK;
+}
+
+}  // namespace ghx

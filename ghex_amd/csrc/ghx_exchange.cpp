@@ -665,6 +665,8 @@ std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, cons
     if (n_items < 1 || !items) throw invalid("need at least one exchange item");
     auto ex = std::make_unique<ghx_exchange>();
     ex->n_items = n_items;
+    for (int32_t i = 0; i < n_items; ++i)
+        ex->only_unstructured = ex->only_unstructured && !cs && items[i].kind == 1;
     std::vector<ghx_pack_entry> rent;              // receive entries, for build_mixed
     std::vector<const halo_entry*> rhalos;         // and their halo entries, for build_cs_self
     for (int dir = 0; dir < 2; ++dir)
@@ -771,6 +773,28 @@ void exchange_plan::make_split()
     }
     split = true;
     for (int dir = 0; dir < 2; ++dir) set_split_parity(dir);
+}
+
+void exchange_plan::make_adjoint(const int32_t* dtypes, int32_t n)
+{
+    if (!only_unstructured)
+        throw invalid("adjoint exchange: the exchange holds a structured or cubed-sphere item (their send "
+                      "boxes overlap; only index-list items have an adjoint)");
+    if (dir_parity[0].word || dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+    if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
+    std::vector<int32_t> dt;
+    for (const ghx_upack_entry& e : uentries[0]) dt.push_back(dtypes[e.field_slot]);
+    // a receive-only item names no contribution entry: its code is checked here
+    for (int32_t i = 0; i < n; ++i)
+        if (dtypes[i] < GHX_DT_F32 || dtypes[i] > GHX_DT_I64)
+            throw invalid("unknown dtype code " + std::to_string(dtypes[i]) + " (GHX_DT_F32, _F64, _I32, _I64)");
+    auto accum = std::make_unique<uaccum_plan>(uentries[0].data(), dt.data(), int(dt.size()), uentries[1].data(),
+                                               int(uentries[1].size()));
+    auto pack = std::make_unique<uplan>(uentries[1].data(), int(uentries[1].size()), 0);
+    adj_accum = std::move(accum);
+    adj_pack = std::move(pack);
 }
 
 int exchange_plan::execute_buffer(int dir, int b, void* const* fptr, int nf, void* const* bptr,

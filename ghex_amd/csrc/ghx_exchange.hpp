@@ -73,6 +73,14 @@ struct exchange_plan
     std::unique_ptr<uput_plan> umixed;
     std::unique_ptr<uplan> upunpack;
     std::string umixed_reason;
+    // the adjoint of an exchange of unstructured items (ghx_uexchange_adjoint_create): the reverse
+    // pack, a pack plan over uentries[1] that gathers the halo cells into the receive buffers, and
+    // the accumulate plan (k_accum_u) with uentries[0] as contribution entries and uentries[1] as
+    // zero entries. Both null until created.
+    bool only_unstructured = true;  // every item is an index-list item (set by make_exchange)
+    std::unique_ptr<uplan> adj_pack;
+    std::unique_ptr<uaccum_plan> adj_accum;
+    void make_adjoint(const int32_t* dtypes, int32_t n);
 
     void make_split();  // the per-buffer plans (ghx_exchange_split)
 

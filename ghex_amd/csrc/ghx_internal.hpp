@@ -314,6 +314,65 @@ struct kargs_um
     uint64_t buf_ptr[GHX_MAX_SLOTS];
 };
 
+// Adjoint accumulate (k_accum_u, ghx_accum.hip): the tables of a uaccum_plan.
+// Destination d (a cell of a field; sum destinations first, sorted by field slot then lid, then
+// the zero destinations, sorted alike) has its lid in the plan's lid table and, a sum
+// destination, its range [first, first + count) of the contribution records in acc_range.
+// A contribution record names (entry, position in that entry's list); records of one destination
+// ascend by (entry, position), which is the order of the adds. The entry record turns (position,
+// level) into a buffer address: element position * pos_stride + level * lev_stride from buf_off
+// on (levels_first: [i][level], strides (levels, 1); else [level][i], strides (1, n)).
+struct acc_range
+{
+    uint32_t first, count;
+};
+struct acc_contrib
+{
+    uint32_t entry, pos;
+};
+struct alignas(16) acc_entry
+{
+    uint64_t buf_off;      // bytes, a multiple of the element size
+    uint32_t n;
+    uint32_t levels;
+    uint32_t levels_first;
+    uint32_t buf_slot;
+    uint32_t pos_stride;   // in elements
+    uint32_t lev_stride;
+};
+static_assert(sizeof(acc_entry) == 32, "acc_entry layout");
+// Tile record, one per workgroup tile: n_rows destinations from first_dest on, all of one field
+// slot (whose descriptor every entry of the slot shares). A lane takes element (row r, level l) of
+// the tile's n_rows * levels: lcontig (levels adjacent in the field) r = e / levels, else
+// l = e / n_rows, `mag` dividing by that. zero: store zero bytes, read nothing.
+struct alignas(16) acc_tile
+{
+    int64_t index_stride_b;
+    int64_t level_stride_b;
+    uint32_t first_dest;
+    uint32_t n_rows;
+    uint32_t levels;
+    magic_u32 mag;
+    uint16_t field_slot;
+    uint8_t dtype;         // GHX_DT_* (a zero tile: any dtype of the slot's element size)
+    uint8_t zero;
+    uint8_t lcontig;
+    uint8_t pad[7];
+};
+static_assert(sizeof(acc_tile) == 48, "acc_tile layout");
+struct kargs_ua
+{
+    const acc_tile* tiles;
+    const acc_range* ranges;
+    const void* lids;          // per destination, int32 or int64 (lid64)
+    const acc_contrib* contribs;
+    const acc_entry* entries;
+    uint32_t n_tiles;
+    uint32_t lid64;
+    uint64_t field_ptr[GHX_MAX_SLOTS];
+    uint64_t buf_ptr[GHX_MAX_SLOTS];
+};
+
 // Double-buffered buffers (the direct exchange's one-launch epochs, ghx_epochs.hip): a buffer
 // exists twice, its odd-parity copy `offset` bytes after the even one, and a launch uses the copy
 // of the exchange's parity, read on the device from the epoch counter (so that a captured graph
@@ -357,6 +416,8 @@ int launch_put_u(const kargs& a, void* stream, uint32_t grid, bool runs);
 int launch_self_u(const kargs& a, void* stream, uint32_t grid, bool runs);
 // self_recs: seg_up records with their buffer side, peer_recs: seg_u tile records (pack)
 int launch_pack_self_u(const kargs_um& a, void* stream, uint32_t grid, bool runs);
+// ghx_accum.hip: the adjoint accumulate over the first a.n_tiles tile records
+int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid);
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

@@ -267,6 +267,41 @@ std::unique_ptr<uput_plan> make_uself(const ghx_upack_entry* src, const ghx_upac
 std::unique_ptr<uput_plan> make_umixed(const ghx_upack_entry* src, const ghx_upack_entry* dst, int n_self,
                                        const ghx_upack_entry* peers, int n_peers);
 
+// Adjoint accumulate (k_accum_u, ghx_accum_plan.cpp): the inverted index of the
+// contribution entries (see include/ghx.h, ghx_uaccum_create). Destinations [0, n_dest) are the
+// sum destinations, sorted by (field slot, lid), the next n_zero_dest the zero destinations,
+// sorted alike; tiles [0, n_sum_tiles) cover the former, the rest the latter, so a launch without
+// zero_halos runs the first n_sum_tiles only. Built without a device; the tables are kept on the
+// host for inspection and uploaded when there is a device.
+struct uaccum_plan
+{
+    uint64_t bytes = 0;                 // buffer bytes read per execution
+    uint64_t n_dest = 0, n_zero_dest = 0;
+    uint32_t max_per_dest = 0;
+    uint32_t n_sum_tiles = 0;
+    bool lid64 = false;
+    int max_field_slot = -1, max_buf_slot = -1;  // of both kinds of entries
+    std::vector<int32_t> dest_slot;     // per destination
+    std::vector<int64_t> dest_lid;
+    std::vector<acc_range> ranges;      // per sum destination
+    std::vector<acc_contrib> contribs;  // by destination, then (entry, position)
+    std::vector<acc_entry> entries;     // per contribution entry
+    std::vector<uint8_t> entry_elem;    // and its element size
+    std::vector<acc_tile> tiles;
+    uint8_t slot_elem[GHX_MAX_SLOTS] = {};  // element size per field slot (0: slot unused)
+    struct tables
+    {
+        void *tiles = nullptr, *ranges = nullptr, *lids = nullptr, *contribs = nullptr, *entries = nullptr;
+        tables() = default;
+        tables(const tables&) = delete;
+        tables& operator=(const tables&) = delete;
+        ~tables();
+    } dev;
+    uaccum_plan(const ghx_upack_entry* contrib, const int32_t* dtypes, int n, const ghx_upack_entry* zero,
+                int n_zero);
+    int execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
+};
+
 // The per-call entry points' plans, cached by content (ghx_cache.cpp): the plan of the call's
 // descriptor and spaces, or index list, is built on first use and executed on `stream`.
 int run_structured(const ghx_field_desc& f, const ghx_box* boxes, int n, int dir, void* field,
@@ -286,4 +321,8 @@ struct ghx_plan : ghx::splan
 struct ghx_uplan : ghx::uplan
 {
     using ghx::uplan::uplan;
+};
+struct ghx_uaccum : ghx::uaccum_plan
+{
+    using ghx::uaccum_plan::uaccum_plan;
 };

@@ -881,6 +881,92 @@ int ghx_uexchange_pack_self(const ghx_exchange* ex, void* const* field_ptrs, int
 int ghx_uexchange_unpack_peers(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                void* const* recv_buffers, int32_t n_recv, ghx_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Adjoint halo exchange of unstructured fields (no reference counterpart): the transpose of the
+ * exchange. Message m of an exchange copies R[r_m[i], l] = S[s_m[i], l]; its adjoint does
+ * S[s_m[i], l] += R[r_m[i], l] for every m, i and level l and then, with zero_halos, sets
+ * R[r_m[i], l] to zero bytes: (owner, halo) -> (owner + sum of halos, 0). It runs as two launches
+ * around the transport: a reverse pack (a ghx_uplan of direction 0 over the RECEIVE lists gathers
+ * the halo cells into the receive buffers), and, once the bytes have travelled back into the SEND
+ * buffers, the accumulate below (k_accum_u), the only kernel that knows an element type.
+ * The sum is bitwise reproducible: no atomics; a destination cell starts from its own value and
+ * adds its contributions one by one in ascending (contribution entry index, position in that
+ * entry's list), in the element type, without reassociation. Integers wrap.
+ * ------------------------------------------------------------------------------------------ */
+#define GHX_DT_F32 1
+#define GHX_DT_F64 2
+#define GHX_DT_I32 3
+#define GHX_DT_I64 4
+
+/* The accumulate plan. contrib[e], e < n, are ghx_upack_entry as the pack entries of an exchange:
+ * the field slot and lids of the OWNER side, the buffer slot and offset of the message, whose
+ * bytes lie as ghx_udata_desc says ([i][level] with levels_first, else [level][i]); dtypes[e] is
+ * the GHX_DT_* code of entry e's elements. zero[k], k < n_zero, name the HALO side (field slot and
+ * lids; buffer members ignored). The planner builds, on the host and without a device: the
+ * destination table (the distinct (field slot, lid) cells of contrib, sorted by slot then lid),
+ * per destination a range of contribution records (entry, position) sorted by (entry, position),
+ * one small record per entry, the distinct zero cells after the sum destinations, and one tile
+ * table of "u_tile_rows" destination rows of one field slot per workgroup. One execution does,
+ * for every sum destination and level, cell = (((cell + c0) + c1) + ...) over its records in
+ * order, each c read from buffer_ptrs[buffer_slot]; with zero_halos != 0 it also stores zero bytes
+ * to every zero cell (with zero_halos == 0 the launch leaves the trailing zero tiles out). One
+ * launch, stream-ordered, never allocates, can be captured. Buffer ranges that overlap are
+ * accepted: contributions are only read.
+ * GHX_ERR_INVALID, with the reason in ghx_last_error(), when: a dtype code is unknown or its size
+ * differs from the entry's elem_size; a zero entry's elem_size is not 4 or 8; levels < 1; a
+ * field or buffer slot is negative or >= 64 (one launch, no launch groups); a list is null with
+ * n_lids > 0, n_lids < 0 or a lid is negative; two entries of one field slot differ in their
+ * descriptor or dtype; buffer_offset is no multiple of the element size; a cell is both a sum
+ * destination and a zero destination; the plan would hold more than 2^32 - 1 contribution
+ * records (or zero cells). Execution refuses pointers that are not aligned to the element. */
+typedef struct ghx_uaccum ghx_uaccum;
+int ghx_uaccum_create(const ghx_upack_entry* contrib, const int32_t* dtypes, int32_t n,
+                      const ghx_upack_entry* zero, int32_t n_zero, ghx_uaccum** out);
+int ghx_uaccum_execute(const ghx_uaccum* p, void* const* field_ptrs, int32_t n_fields,
+                       void* const* buffer_ptrs, int32_t n_buffers, int32_t zero_halos,
+                       ghx_stream stream);
+/* buffer bytes read per execution, sum destinations, zero destinations, contribution records, the
+ * most records of one destination, workgroup tiles (sum and zero tiles) */
+int ghx_uaccum_info(const ghx_uaccum* p, uint64_t* bytes, int64_t* n_dest, int64_t* n_zero_dest,
+                    int64_t* n_contrib, int64_t* max_per_dest, int32_t* n_tiles);
+/* Destination k of the plan (host only, the twin of ghx_uself_segment), k in [0, n_dest +
+ * n_zero_dest): its cell, and for a sum destination its records [first, first + count) of
+ * ghx_uaccum_contrib; a zero destination has zero = 1 and no records. */
+typedef struct ghx_uaccum_dest_info
+{
+    int32_t field_slot;
+    int32_t zero;
+    int64_t lid;
+    int64_t first;
+    int64_t count;
+} ghx_uaccum_dest_info;
+int ghx_uaccum_dest(const ghx_uaccum* p, int64_t k, ghx_uaccum_dest_info* out);
+/* Contribution record j in [0, n_contrib): the contribution entry and the position in its list. */
+int ghx_uaccum_contrib(const ghx_uaccum* p, int64_t j, int32_t* entry, int64_t* pos);
+int ghx_uaccum_destroy(ghx_uaccum* p);
+
+/* The adjoint of an exchange of unstructured items. ghx_uexchange_adjoint_create builds and
+ * attaches two plans (setup time, synchronous upload, as ghx_exchange_split attaches its plans):
+ * the reverse pack, a ghx_uplan of direction 0 over the exchange's unpack entries, and the
+ * accumulate plan with the exchange's pack entries as contribution entries and its unpack entries
+ * as zero entries. dtypes[i] is the GHX_DT_* code of item i (n_items: the exchange's).
+ * GHX_ERR_INVALID, with the reason, for an exchange that holds a structured or cubed-sphere item,
+ * while a direction has parity set (ghx_exchange_set_parity), and for ghx_uaccum_create's
+ * reasons. ghx_uexchange_adjoint_info works on any exchange: *ready = 1 once the plans exist.
+ * ghx_uexchange_adjoint_pack has ghx_exchange_unpack's argument contract (it writes the RECEIVE
+ * buffers), ghx_uexchange_adjoint_accumulate ghx_exchange_pack's (it reads the SEND buffers);
+ * the caller moves the bytes of every receive buffer into the send buffer of the same message
+ * between them (a self message's receive buffer is its send buffer). Both fail with
+ * GHX_ERR_INVALID before create and while a direction has parity set. */
+int ghx_uexchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items);
+int ghx_uexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_dest,
+                               int64_t* n_contrib);
+int ghx_uexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                               void* const* recv_buffers, int32_t n_recv, ghx_stream stream);
+int ghx_uexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
+                                     int32_t n_fields, void* const* send_buffers, int32_t n_send,
+                                     int32_t zero_halos, ghx_stream stream);
+
 /* Device-side access epochs of the zero-copy exchanges (bulk puts, direct pack): the reference's
  * access guards (include/ghex/rma/access_guard.hpp:35-140; per range: start/end_target_epoch on
  * the owner, start/end_source_epoch on the putter; include/ghex/bulk_communication_object.hpp
