@@ -83,6 +83,12 @@ class UAccumDestInfo(ctypes.Structure):
                 ("count", c_i64)]
 
 
+class SAccumBoxInfo(ctypes.Structure):
+    _fields_ = [("field_slot", c_i32), ("zero", c_i32), ("first", c_i32 * MAX_DIM),
+                ("last", c_i32 * MAX_DIM), ("row_elems", c_i64), ("wlog2", c_i32), ("pad", c_i32),
+                ("first_src", c_i64), ("n_src", c_i64)]
+
+
 # element type codes of the adjoint accumulate (GHX_DT_*, include/ghx.h)
 DT_F32, DT_F64, DT_I32, DT_I64 = 1, 2, 3, 4
 
@@ -164,6 +170,16 @@ _SIGS = {
     "ghx_uexchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64)]),
     "ghx_uexchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_uexchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
+    "ghx_saccum_create": (c_i32, [P(PackEntry), P(c_i32), c_i32, P(PackEntry), c_i32, P(c_vp)]),
+    "ghx_saccum_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
+    "ghx_saccum_info": (c_i32, [c_vp, P(c_u64), P(c_i64), P(c_i64), P(c_i64), P(c_i64), P(c_i32)]),
+    "ghx_saccum_box": (c_i32, [c_vp, c_i64, P(SAccumBoxInfo)]),
+    "ghx_saccum_source": (c_i32, [c_vp, c_i64, P(c_i32), P(c_i32), P(c_i32), P(c_u64)]),
+    "ghx_saccum_destroy": (c_i32, [c_vp]),
+    "ghx_sexchange_adjoint_create": (c_i32, [c_vp, P(c_i32), c_i32]),
+    "ghx_sexchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64)]),
+    "ghx_sexchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_sexchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
                               c_i32, c_vp]),
     "ghx_udomain_create": (c_i32, [c_i32, P(c_i64), c_i64, P(c_i64), c_i64, P(c_vp)]),

@@ -252,7 +252,8 @@ class CommunicationObject:
     def __init__(self, context, fuse_self: bool = True, staging=None, pipelined: bool = False,
                  rccl_self: bool = False, max_streams: int = 4, copy_engine: str = "probe",
                  direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False,
-                 fuse_lists: bool = False, fuse_lists_mixed: bool = False):
+                 fuse_lists: bool = False, fuse_lists_mixed: bool = False,
+                 adjoint_boxes: bool = False):
         if staging not in (None, "host"):
             raise ValueError("staging must be None (device buffers) or 'host'")
         if direct and (staging is not None or pipelined or rccl_self):
@@ -283,6 +284,10 @@ class CommunicationObject:
         # messages, the unpack launch covers the peers only (ghx_uexchange_pack_self,
         # ghx_uexchange_unpack_peers). Opt-in; a plan without that form takes the usual path
         self.fuse_lists_mixed = bool(fuse_lists_mixed)
+        # regular structured fields in the adjoint exchange: their overlapping send boxes are
+        # summed through an arrangement of sub-boxes (ghx_sexchange_adjoint_*, k_accum_s). Opt-in;
+        # without it the adjoint exchange takes unstructured fields only, as before
+        self.adjoint_boxes = bool(adjoint_boxes)
         self.staging = staging
         self.pipelined = pipelined
         # tests: route the self messages through RCCL too (a 1-rank communicator), so the
@@ -568,23 +573,37 @@ class CommunicationObject:
     # -- adjoint exchange ------------------------------------------------------------------------
     def _adjoint_plan(self, bis):
         """The plan of `bis` with its adjoint plans attached (built on first use): the reverse
-        pack and the accumulate (ghx_uexchange_adjoint_create, k_accum_u)."""
+        pack and the accumulate (ghx_uexchange_adjoint_create, k_accum_u; with adjoint_boxes and
+        regular structured fields ghx_sexchange_adjoint_create, k_accum_s)."""
         if self.direct or self.pipelined:
             raise ValueError("the adjoint exchange is the plain communication object's "
                              "(no direct=True, no pipelined=True)")
+        boxes = self.adjoint_boxes and any(
+            bi.field.kind != 1 or getattr(bi.field, "cs_item", None) is not None for bi in bis)
         for bi in bis:
-            if bi.field.kind != 1 or getattr(bi.field, "cs_item", None) is not None:
+            cs = getattr(bi.field, "cs_item", None) is not None
+            if boxes and cs:
+                raise ValueError("the adjoint exchange of boxes takes regular structured fields "
+                                 "(a cubed-sphere adjoint would rotate and flip signs)")
+            if boxes and bi.field.kind != 0:
+                raise ValueError("the adjoint exchange takes structured fields or unstructured "
+                                 "fields, not both in one call")
+            if not boxes and (bi.field.kind != 1 or cs):
                 raise ValueError("the adjoint exchange takes unstructured fields only (structured "
                                  "and cubed-sphere send boxes overlap)")
         codes = [bi.field.dtype_code() for bi in bis]  # TypeError for any other dtype
         plan = self.plan(bis)
         if getattr(plan, "_adjoint_codes", None) != codes:
-            _ghx.call("ghx_uexchange_adjoint_create", plan.h, _ghx.i32_array(codes), len(codes))
+            # boxes: ghx_sexchange_adjoint_* (k_accum_s), lists: ghx_uexchange_adjoint_* (k_accum_u)
+            prefix = "ghx_sexchange_adjoint_" if boxes else "ghx_uexchange_adjoint_"
+            _ghx.call(prefix + "create", plan.h, _ghx.i32_array(codes), len(codes))
             plan._adjoint_codes = codes
+            plan._adjoint_prefix = prefix
         return plan
 
     def adjoint_exchange(self, *buffer_infos, zero_halos: bool = True) -> CommunicationHandle:
-        """The transpose of exchange() for unstructured fields, non-blocking on the current
+        """The transpose of exchange() for unstructured fields and, on an object made with
+        adjoint_boxes=True, for regular structured fields, non-blocking on the current
         stream: every halo cell's value is sent back to the cell's owner and added to it, in a
         fixed order (bitwise reproducible, no atomics); with zero_halos the halo cells are then
         set to zero (the true transpose), without it they keep their values (assembly). The plain
@@ -617,7 +636,7 @@ class CommunicationObject:
         sptrs = _ghx.ptr_array([t.data_ptr() for t in send])
         rptrs = _ghx.ptr_array([t.data_ptr() for t in recv])
         with torch.cuda.stream(stream):
-            _ghx.call("ghx_uexchange_adjoint_pack", plan.h, fptrs, len(bis), rptrs, len(recv),
+            _ghx.call(plan._adjoint_prefix + "pack", plan.h, fptrs, len(bis), rptrs, len(recv),
                       stream.cuda_stream)
             # the forward transport with the roles swapped: peer receive buffers are sent, peer
             # send buffers receive; tags as they are. A self message's receive buffer is its
@@ -632,7 +651,7 @@ class CommunicationObject:
             else:
                 for w in route(self.context, sends, recvs):
                     w.wait()
-            _ghx.call("ghx_uexchange_adjoint_accumulate", plan.h, fptrs, len(bis), sptrs,
+            _ghx.call(plan._adjoint_prefix + "accumulate", plan.h, fptrs, len(bis), sptrs,
                       len(send), 1 if zero_halos else 0, stream.cuda_stream)
             ev = self._done_event(stream)
         self._valid = True
@@ -644,7 +663,7 @@ class CommunicationObject:
         plan = self._adjoint_plan(bis)
         send, recv = self.buffers(plan, bis[0].field.device)
         s = (stream or torch.cuda.current_stream()).cuda_stream
-        _ghx.call("ghx_uexchange_adjoint_pack", plan.h,
+        _ghx.call(plan._adjoint_prefix + "pack", plan.h,
                   _ghx.ptr_array([b.field.data_ptr() for b in bis]), len(bis),
                   _ghx.ptr_array([t.data_ptr() for t in recv]), len(recv), s)
         return plan, send, recv
@@ -656,7 +675,7 @@ class CommunicationObject:
         plan = self._adjoint_plan(bis)
         send, recv = self.buffers(plan, bis[0].field.device)
         s = (stream or torch.cuda.current_stream()).cuda_stream
-        _ghx.call("ghx_uexchange_adjoint_accumulate", plan.h,
+        _ghx.call(plan._adjoint_prefix + "accumulate", plan.h,
                   _ghx.ptr_array([b.field.data_ptr() for b in bis]), len(bis),
                   _ghx.ptr_array([t.data_ptr() for t in send]), len(send),
                   1 if zero_halos else 0, s)

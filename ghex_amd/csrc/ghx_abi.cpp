@@ -1335,6 +1335,145 @@ int ghx_uexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_
     });
 }
 
+int ghx_saccum_create(const ghx_pack_entry* contrib, const int32_t* dtypes, int32_t n,
+                      const ghx_pack_entry* zero, int32_t n_zero, ghx_saccum** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        *out = nullptr;
+        if (n < 0 || n_zero < 0 || (n && (!contrib || !dtypes)) || (n_zero && !zero))
+            throw invalid("bad entry arrays");
+        *out = new ghx_saccum(contrib, dtypes, n, zero, n_zero);
+        return GHX_OK;
+    });
+}
+
+int ghx_saccum_execute(const ghx_saccum* p, void* const* field_ptrs, int32_t n_fields,
+                       void* const* buffer_ptrs, int32_t n_buffers, int32_t zero_halos,
+                       ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        return p->execute(field_ptrs, n_fields, buffer_ptrs, n_buffers, zero_halos != 0, stream);
+    });
+}
+
+int ghx_saccum_info(const ghx_saccum* p, uint64_t* bytes, int64_t* n_boxes, int64_t* n_zero_boxes,
+                    int64_t* n_sources, int64_t* max_sources, int32_t* n_tiles)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (bytes) *bytes = p->bytes;
+        if (n_boxes) *n_boxes = int64_t(p->n_sum_boxes);
+        if (n_zero_boxes) *n_zero_boxes = int64_t(p->boxes.size()) - int64_t(p->n_sum_boxes);
+        if (n_sources) *n_sources = int64_t(p->srcs.size());
+        if (max_sources) *max_sources = p->max_sources;
+        if (n_tiles) *n_tiles = int32_t(p->tiles.size());
+        return GHX_OK;
+    });
+}
+
+int ghx_saccum_box(const ghx_saccum* p, int64_t k, ghx_saccum_box_info* out)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        check_ptr(out, "out");
+        if (k < 0 || uint64_t(k) >= p->boxes.size()) throw invalid("sub-box index out of range");
+        const saccum_box& b = p->boxes[size_t(k)];
+        *out = ghx_saccum_box_info{};
+        out->field_slot = b.field_slot;
+        out->zero = b.zero ? 1 : 0;
+        for (int d = 0; d < GHX_MAX_DIM; ++d)
+        {
+            out->first[d] = b.first[d];
+            out->last[d] = b.last[d];
+        }
+        out->row_elems = int64_t(b.row_elems);
+        out->wlog2 = b.wlog2;
+        out->first_src = b.zero ? 0 : int64_t(b.first_src);
+        out->n_src = int64_t(b.n_src);
+        return GHX_OK;
+    });
+}
+
+int ghx_saccum_source(const ghx_saccum* p, int64_t j, int32_t* entry, int32_t* box, int32_t* buffer_slot,
+                      uint64_t* buffer_offset_of_origin)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (j < 0 || uint64_t(j) >= p->srcs.size()) throw invalid("source index out of range");
+        if (entry) *entry = int32_t(p->src_entry[size_t(j)]);
+        if (box) *box = int32_t(p->src_box[size_t(j)]);
+        if (buffer_slot) *buffer_slot = int32_t(p->srcs[size_t(j)].buf_slot);
+        if (buffer_offset_of_origin) *buffer_offset_of_origin = p->srcs[size_t(j)].buf_off;
+        return GHX_OK;
+    });
+}
+
+int ghx_saccum_destroy(ghx_saccum* p)
+{
+    return guarded([&] {
+        delete p;
+        return GHX_OK;
+    });
+}
+
+int ghx_sexchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        ex->make_sadjoint(dtypes, n_items);
+        return GHX_OK;
+    });
+}
+
+int ghx_sexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_boxes, int64_t* n_sources)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(ready, "ready");
+        const saccum_plan* p = ex->sadj_accum.get();
+        *ready = p ? 1 : 0;
+        if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
+        if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
+        return GHX_OK;
+    });
+}
+
+namespace
+{
+void check_sadjoint(const ghx_exchange* ex)
+{
+    check_ptr(ex, "exchange");
+    if (!ex->sadj_accum || !ex->sadj_pack)
+        throw invalid("adjoint exchange: no adjoint plans (ghx_sexchange_adjoint_create)");
+    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+}
+}  // namespace
+
+int ghx_sexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                               void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
+{
+    return guarded([&] {
+        check_sadjoint(ex);
+        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
+        return ex->sadj_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+    });
+}
+
+int ghx_sexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
+                                     int32_t n_fields, void* const* send_buffers, int32_t n_send,
+                                     int32_t zero_halos, ghx_stream stream)
+{
+    return guarded([&] {
+        check_sadjoint(ex);
+        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
+        return ex->sadj_accum->execute(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
+    });
+}
+
 int ghx_uput_segment(const ghx_put* put, int32_t k, ghx_uput_segment_info* out)
 {
     return guarded([&] {

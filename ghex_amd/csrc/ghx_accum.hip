@@ -1,4 +1,5 @@
-// ghx_accum.hip — gfx950 (CDNA4) adjoint accumulate for index-list halos (k_accum_u).
+// ghx_accum.hip — gfx950 (CDNA4) adjoint accumulate for index-list halos (k_accum_u) and, further
+// down, for structured fields (k_accum_s).
 //
 // The adjoint of the halo exchange sends every halo copy of a cell back to the cell's owner and
 // sums it there. The contributions are already stored once: they are the message bytes a reverse
@@ -149,7 +150,178 @@ __global__ __launch_bounds__(kBlock) void k_accum_u(kargs_ua a)
         else accum_tile<uint32_t>(a, s);
     }
 }
+// ---------------------------------------------------------------------------------------------
+// k_accum_s: the adjoint accumulate of structured fields (saccum_plan, ghx_saccum_plan.cpp).
+//
+// A field's send boxes overlap, so the planner has cut their union into disjoint sub-boxes whose
+// cells all have the same sources. A workgroup takes one tile of one sub-box (its record at the
+// tile's index), a lane one vector of up to 16 B of a row: it loads the cell vector once, walks
+// the sub-box's source records in list order — ascending (entry, box) — and stores the cell once.
+// The tile and source records are the same for the whole workgroup and are read through the
+// constant address space (scalar loads); what a lane issues is payload only: one load of the cell,
+// one load per source, one store. The loads of kAccBatch sources are issued together, the adds
+// stay in list order per element of the vector; the list's remainder (1 to 3 sources, uniform)
+// loads exactly those, so a list of one — a face — takes no duplicate load. Zero tiles store zero
+// vectors and load nothing from the field. 64-bit offsets, no LDS, no atomics.
+// ---------------------------------------------------------------------------------------------
+#define GHX_CONST __attribute__((address_space(4)))
+
+template<typename T, int N>
+struct vec_of
+{
+    typedef T type __attribute__((ext_vector_type(N)));
+};
+template<typename T>
+struct vec_of<T, 1>
+{
+    typedef T type;
+};
+
+__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return uint64_t(lo) | (uint64_t(hi) << 32); }
+
+__device__ __forceinline__ sacc_tile load_tile_s(const GHX_CONST sacc_tile* tiles, uint32_t t)
+{
+    const GHX_CONST u32x4* p = (const GHX_CONST u32x4*)(tiles + t);
+    u32x4 r[sizeof(sacc_tile) / 16];
+#pragma unroll
+    for (uint32_t k = 0; k < sizeof(sacc_tile) / 16; ++k) r[k] = p[k];
+    sacc_tile s;
+    __builtin_memcpy(&s, r, sizeof(sacc_tile));
+    return s;
+}
+
+// the vector of source record j that lies at outer coordinates c, byte column col of a sub-box row
+template<typename V>
+__device__ __forceinline__ V load_src(const kargs_sa& a, const GHX_CONST sacc_src* srcs, uint32_t j,
+                                      const uint32_t (&c)[4], uint32_t col, bool deep)
+{
+    const GHX_CONST u32x4* p = (const GHX_CONST u32x4*)(srcs + j);
+    const u32x4 r0 = p[0], r1 = p[1], r2 = p[2];  // buf_off, stride[0] | stride[1], [2] | [3], slot
+    const char* b = reinterpret_cast<const char*>(a.buf_ptr[r2.z]) + u64_of(r0.x, r0.y);
+    uint64_t off = uint64_t(c[0]) * u64_of(r0.z, r0.w) + uint64_t(c[1]) * u64_of(r1.x, r1.y) + col;
+    if (deep) off += uint64_t(c[2]) * u64_of(r1.z, r1.w) + uint64_t(c[3]) * u64_of(r2.x, r2.y);
+    return *(const GHX_GLOBAL V*)(b + off);
+}
+
+template<typename T, int W>
+__device__ __forceinline__ void accum_tile_s(const kargs_sa& a, const sacc_tile& s, const GHX_CONST sacc_src* srcs)
+{
+    typedef typename vec_of<T, W / int(sizeof(T))>::type V;
+    constexpr int w = W == 16 ? 4 : W == 8 ? 3 : 2;
+    char* field = reinterpret_cast<char*>(a.field_ptr[s.field_slot]) + s.field_off;
+    const bool deep = s.n_outer > 2;
+    const uint32_t nv = sacc_vectors(s, w);
+    for (uint32_t i = threadIdx.x; i < nv; i += kBlock)
+    {
+        uint32_t c[4], col;
+        sacc_decode(s, i, w, c, col);
+        int64_t foff = int64_t(c[0]) * s.stride[0] + int64_t(c[1]) * s.stride[1] + int64_t(col);
+        if (deep) foff += int64_t(c[2]) * s.stride[2] + int64_t(c[3]) * s.stride[3];
+        GHX_GLOBAL V* cell = (GHX_GLOBAL V*)(field + foff);
+        V acc = *cell;
+        uint32_t j = s.first_src, left = s.n_src;  // uniform
+        while (left >= uint32_t(kAccBatch))
+        {
+            V v[kAccBatch];
+#pragma unroll
+            for (uint32_t k = 0; k < kAccBatch; ++k) v[k] = load_src<V>(a, srcs, j + k, c, col, deep);
+#pragma unroll
+            for (uint32_t k = 0; k < kAccBatch; ++k) acc = acc + v[k];
+            j += kAccBatch;
+            left -= kAccBatch;
+        }
+        if (left == 3)
+        {
+            const V v0 = load_src<V>(a, srcs, j, c, col, deep), v1 = load_src<V>(a, srcs, j + 1, c, col, deep),
+                    v2 = load_src<V>(a, srcs, j + 2, c, col, deep);
+            acc = acc + v0;
+            acc = acc + v1;
+            acc = acc + v2;
+        }
+        else if (left == 2)
+        {
+            const V v0 = load_src<V>(a, srcs, j, c, col, deep), v1 = load_src<V>(a, srcs, j + 1, c, col, deep);
+            acc = acc + v0;
+            acc = acc + v1;
+        }
+        else if (left == 1)
+            acc = acc + load_src<V>(a, srcs, j, c, col, deep);
+        *cell = acc;
+    }
+}
+
+template<int W>
+__device__ __forceinline__ void zero_tile_s(const kargs_sa& a, const sacc_tile& s)
+{
+    typedef typename vec_of<uint32_t, W / 4>::type V;
+    constexpr int w = W == 16 ? 4 : W == 8 ? 3 : 2;
+    char* field = reinterpret_cast<char*>(a.field_ptr[s.field_slot]) + s.field_off;
+    const uint32_t nv = sacc_vectors(s, w);
+    for (uint32_t i = threadIdx.x; i < nv; i += kBlock)
+    {
+        uint32_t c[4], col;
+        sacc_decode(s, i, w, c, col);
+        const int64_t foff = int64_t(c[0]) * s.stride[0] + int64_t(c[1]) * s.stride[1] + int64_t(c[2]) * s.stride[2] +
+                             int64_t(c[3]) * s.stride[3] + int64_t(col);
+        *(GHX_GLOBAL V*)(field + foff) = V(0);
+    }
+}
+
+template<typename T>
+__device__ __forceinline__ void accum_tile_sw(const kargs_sa& a, const sacc_tile& s, const GHX_CONST sacc_src* srcs, int w)
+{
+    if (w == 4) accum_tile_s<T, 16>(a, s, srcs);
+    else if constexpr (sizeof(T) == 8) accum_tile_s<T, 8>(a, s, srcs);
+    else if (w == 3) accum_tile_s<T, 8>(a, s, srcs);
+    else accum_tile_s<T, 4>(a, s, srcs);
+}
+
+__global__ __launch_bounds__(kBlock) void k_accum_s(kargs_sa a)
+{
+    const GHX_CONST sacc_tile* tiles = (const GHX_CONST sacc_tile*)reinterpret_cast<uintptr_t>(a.tiles);
+    const GHX_CONST sacc_src* srcs = (const GHX_CONST sacc_src*)reinterpret_cast<uintptr_t>(a.srcs);
+    for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x)
+    {
+        const sacc_tile s = load_tile_s(tiles, t);
+        const int w = sacc_width(s, a.field_ptr[s.field_slot], a.buf_mis8, a.buf_mis16);
+        if (s.zero)
+        {
+            if (w == 4) zero_tile_s<16>(a, s);
+            else if (w == 3) zero_tile_s<8>(a, s);
+            else zero_tile_s<4>(a, s);
+        }
+        else if (s.dtype == GHX_DT_F32) accum_tile_sw<float>(a, s, srcs, w);
+        else if (s.dtype == GHX_DT_F64) accum_tile_sw<double>(a, s, srcs, w);
+        else if (s.dtype == GHX_DT_I64) accum_tile_sw<uint64_t>(a, s, srcs, w);
+        else accum_tile_sw<uint32_t>(a, s, srcs, w);
+    }
+}
 }  // namespace
+
+int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid)
+{
+    if (a.n_tiles == 0) return GHX_OK;
+    grid = grid < a.n_tiles ? grid : a.n_tiles;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (t_timing && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
+    {
+        hipExtLaunchKernelGGL(k_accum_s, dim3(grid), dim3(kBlock), 0, s, e0, e1, 0, a);
+        t_timing->emplace_back(e0, e1);
+    }
+    else
+    {
+        if (e0) (void)hipEventDestroy(e0);
+        hipLaunchKernelGGL(k_accum_s, dim3(grid), dim3(kBlock), 0, s, a);
+    }
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess)
+    {
+        set_error(std::string("structured adjoint accumulate kernel launch failed: ") + hipGetErrorString(err));
+        return GHX_ERR_HIP;
+    }
+    return GHX_OK;
+}
 
 int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid)
 {

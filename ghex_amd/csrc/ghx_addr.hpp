@@ -41,6 +41,37 @@ GHX_HD int64_t field_offset_s(const seg_s& s, uint32_t p)
            int64_t(c2) * s.stride[2] + int64_t(q2) * s.stride[3] + int64_t(col);
 }
 
+// Adjoint accumulate tile (sacc_tile): the vectors a launch of width log2 w (<= s.wlog2) takes
+// from it, and vector i's place: the outer coordinates c of its row and its byte column in the row.
+// A planned vector (1 << wlog2 bytes) splits into 1 << (wlog2 - w) narrowed ones.
+GHX_HD uint32_t sacc_vectors(const sacc_tile& s, int w) { return (s.n_rows * (s.len >> s.wlog2)) << (s.wlog2 - w); }
+
+GHX_HD void sacc_decode(const sacc_tile& s, uint32_t i, int w, uint32_t (&c)[4], uint32_t& col)
+{
+    const int k = s.wlog2 - w;
+    const uint32_t e = i >> k, sub = i & ((1u << k) - 1u);
+    const uint32_t r = fastdiv(e, s.mag_vec);
+    const uint32_t v = e - r * (s.len >> s.wlog2);
+    col = s.col0 + (v << s.wlog2) + (sub << w);
+    const uint32_t row = s.first_row + r;
+    const uint32_t q0 = fastdiv(row, s.mag_ext[0]);
+    c[0] = row - q0 * s.ext[0];
+    const uint32_t q1 = fastdiv(q0, s.mag_ext[1]);
+    c[1] = q0 - q1 * s.ext[1];
+    c[3] = fastdiv(q1, s.mag_ext[2]);
+    c[2] = q1 - c[3] * s.ext[2];
+}
+
+// the launch's vector width of a tile: the plan's, narrowed by the field pointer and by the buffer
+// pointers the tile's sources read (mis8 / mis16: the slots whose pointer is not 8 / 16-B aligned)
+GHX_HD int sacc_width(const sacc_tile& s, uint64_t field_ptr, uint64_t mis8, uint64_t mis16)
+{
+    int w = s.wlog2;
+    if ((field_ptr & 15u) || (s.buf_mask & mis16)) w = w < 3 ? w : 3;
+    if ((field_ptr & 7u) || (s.buf_mask & mis8)) w = w < 2 ? w : 2;
+    return w;
+}
+
 // Coordinates of lane index i in a tile record's decode radix (tdim); false where they fall
 // outside this tile's own extents (act: the last tile along an axis).
 GHX_HD bool tile_decode(const seg_x& s, uint32_t i, uint32_t (&c)[4])

@@ -666,7 +666,11 @@ std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, cons
     auto ex = std::make_unique<ghx_exchange>();
     ex->n_items = n_items;
     for (int32_t i = 0; i < n_items; ++i)
+    {
         ex->only_unstructured = ex->only_unstructured && !cs && items[i].kind == 1;
+        ex->only_structured = ex->only_structured && items[i].kind == 0;
+    }
+    ex->cubed_sphere = cs != nullptr;
     std::vector<ghx_pack_entry> rent;              // receive entries, for build_mixed
     std::vector<const halo_entry*> rhalos;         // and their halo entries, for build_cs_self
     for (int dir = 0; dir < 2; ++dir)
@@ -795,6 +799,31 @@ void exchange_plan::make_adjoint(const int32_t* dtypes, int32_t n)
     auto pack = std::make_unique<uplan>(uentries[1].data(), int(uentries[1].size()), 0);
     adj_accum = std::move(accum);
     adj_pack = std::move(pack);
+}
+
+void exchange_plan::make_sadjoint(const int32_t* dtypes, int32_t n)
+{
+    if (cubed_sphere)
+        throw invalid("adjoint exchange: the exchange holds a cubed-sphere item (its adjoint would rotate and "
+                      "flip signs; only regular structured items take ghx_sexchange_adjoint_create)");
+    if (!only_structured)
+        throw invalid("adjoint exchange: the exchange holds an unstructured item (an exchange mixing structured "
+                      "and unstructured items has no adjoint; index-list items take ghx_uexchange_adjoint_create)");
+    if (dir_parity[0].word || dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+    if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
+    // a receive-only item names no contribution entry: its code is checked here
+    for (int32_t i = 0; i < n; ++i)
+        if (dtypes[i] < GHX_DT_F32 || dtypes[i] > GHX_DT_I64)
+            throw invalid("unknown dtype code " + std::to_string(dtypes[i]) + " (GHX_DT_F32, _F64, _I32, _I64)");
+    std::vector<int32_t> dt;
+    for (const ghx_pack_entry& e : entries[0]) dt.push_back(dtypes[e.field_slot]);
+    auto accum = std::make_unique<saccum_plan>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
+                                               int(entries[1].size()));
+    auto pack = std::make_unique<splan>(entries[1].data(), int(entries[1].size()), 0);
+    sadj_accum = std::move(accum);
+    sadj_pack = std::move(pack);
 }
 
 int exchange_plan::execute_buffer(int dir, int b, void* const* fptr, int nf, void* const* bptr,

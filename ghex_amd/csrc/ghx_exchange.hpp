@@ -81,6 +81,14 @@ struct exchange_plan
     std::unique_ptr<uplan> adj_pack;
     std::unique_ptr<uaccum_plan> adj_accum;
     void make_adjoint(const int32_t* dtypes, int32_t n);
+    // the adjoint of an exchange of regular structured items (ghx_sexchange_adjoint_create): the
+    // reverse pack, a pack plan over entries[1], and the accumulate plan (k_accum_s) with entries[0]
+    // as contribution entries and entries[1] as zero entries. Both null until created.
+    bool only_structured = true;  // every item is a regular structured item (set by make_exchange)
+    bool cubed_sphere = false;    // made by ghx_cs_exchange_create
+    std::unique_ptr<splan> sadj_pack;
+    std::unique_ptr<saccum_plan> sadj_accum;
+    void make_sadjoint(const int32_t* dtypes, int32_t n);
 
     void make_split();  // the per-buffer plans (ghx_exchange_split)
 

@@ -373,6 +373,62 @@ struct kargs_ua
     uint64_t buf_ptr[GHX_MAX_SLOTS];
 };
 
+// Adjoint accumulate of structured fields (k_accum_s, ghx_accum.hip): the tables
+// of a saccum_plan. The union of a field's contribution boxes is cut into disjoint sub-boxes; every
+// cell of a sub-box has the same sources — the contribution boxes that hold it, in ascending
+// (entry, box) — so the source list belongs to the sub-box and is uniform over a workgroup.
+// A sub-box is a set of equal rows (runs along the layout's fastest dimension; one element each
+// where that dimension is strided in the field) decoded from the row index as seg_s's rows are:
+// outer coordinate c_k = (row / (ext[0] .. ext[k-1])) % ext[k], row at field_off + sum c_k *
+// stride[k]. A row is a contiguous piece of one buffer row of each source: the source record holds
+// the buffer offset of the sub-box's origin in that box's dense buffer box and the box's buffer
+// byte strides for the same outer coordinates.
+struct alignas(16) sacc_src
+{
+    uint64_t buf_off;     // byte offset in the buffer of the sub-box's origin
+    uint64_t stride[4];   // buffer byte stride of outer dim k of the sub-box in this box
+    uint32_t buf_slot;
+    uint32_t pad;
+};
+static_assert(sizeof(sacc_src) == 48, "sacc_src layout");
+// Tile record, one per workgroup tile: the sub-box with the tile's part of it — n_rows rows from
+// first_row on, of each the `len` bytes from byte col0 on (col0 > 0 only where one row is longer
+// than a tile: then n_rows = 1 and col0 a multiple of 16). A lane takes one vector of the tile's
+// n_rows * len bytes, rows outermost. zero: store zero bytes, read nothing (no sources).
+struct alignas(16) sacc_tile
+{
+    int64_t field_off;    // field byte offset of the sub-box's origin
+    int64_t stride[4];    // field byte stride of outer dim k (k = 0 varies fastest over rows)
+    uint64_t buf_mask;    // bit b: a source of the sub-box reads buffer slot b
+    uint32_t ext[4];      // outer extents (1 for unused dims)
+    magic_u32 mag_ext[3]; // division by ext[0], ext[1], ext[2]
+    magic_u32 mag_vec;    // division by len >> wlog2, the planned vectors of a row piece
+    uint32_t len;         // bytes of a row this tile covers (the row length unless col0 / cut)
+    uint32_t col0;
+    uint32_t first_row;
+    uint32_t n_rows;
+    uint32_t first_src;   // the sub-box's records [first_src, first_src + n_src) of sacc_src
+    uint32_t n_src;
+    uint16_t field_slot;
+    uint8_t dtype;        // GHX_DT_* (a zero tile: any dtype of the slot's element size)
+    uint8_t zero;
+    uint8_t wlog2;        // log2 of the widest vector (<= 16 B) dividing the row, the field offset
+                          // and strides and every source's buffer offset and strides
+    uint8_t n_outer;
+    uint8_t pad[2];
+};
+static_assert(sizeof(sacc_tile) == 128, "sacc_tile layout");
+struct kargs_sa
+{
+    const sacc_tile* tiles;
+    const sacc_src* srcs;
+    uint32_t n_tiles;
+    uint32_t pad;
+    uint64_t buf_mis8, buf_mis16;  // bit b: buffer pointer b is not 8- / 16-byte aligned
+    uint64_t field_ptr[GHX_MAX_SLOTS];
+    uint64_t buf_ptr[GHX_MAX_SLOTS];
+};
+
 // Double-buffered buffers (the direct exchange's one-launch epochs, ghx_epochs.hip): a buffer
 // exists twice, its odd-parity copy `offset` bytes after the even one, and a launch uses the copy
 // of the exchange's parity, read on the device from the epoch counter (so that a captured graph
@@ -418,6 +474,7 @@ int launch_self_u(const kargs& a, void* stream, uint32_t grid, bool runs);
 int launch_pack_self_u(const kargs_um& a, void* stream, uint32_t grid, bool runs);
 // ghx_accum.hip: the adjoint accumulate over the first a.n_tiles tile records
 int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid);
+int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid);
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

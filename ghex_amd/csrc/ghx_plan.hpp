@@ -302,6 +302,44 @@ struct uaccum_plan
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
 };
 
+// Adjoint accumulate of structured fields (k_accum_s, ghx_saccum_plan.cpp): the
+// arrangement of the contribution boxes (see include/ghx.h, ghx_saccum_create). Sub-boxes
+// [0, n_sum_boxes) are the sum sub-boxes, by field slot, the rest the zero entries' boxes; tiles
+// [0, n_sum_tiles) cover the former, so a launch without zero_halos runs those only. Built without
+// a device; the tables are kept on the host for inspection and uploaded when there is a device.
+struct saccum_box
+{
+    int32_t field_slot;
+    bool zero;
+    int32_t first[GHX_MAX_DIM], last[GHX_MAX_DIM];  // spatial dims, the field's local coordinates
+    uint64_t row_elems;
+    uint8_t wlog2;
+    uint32_t first_src, n_src;
+};
+struct saccum_plan
+{
+    uint64_t bytes = 0;                  // buffer bytes read per execution
+    uint32_t n_sum_boxes = 0, n_sum_tiles = 0, max_sources = 0;
+    int max_field_slot = -1, max_buf_slot = -1;  // of both kinds of entries
+    std::vector<saccum_box> boxes;
+    std::vector<sacc_src> srcs;          // by sub-box, each list in ascending (entry, box)
+    std::vector<uint32_t> src_entry, src_box;  // per source record: the contribution box it is
+    std::vector<sacc_tile> tiles;
+    uint8_t slot_elem[GHX_MAX_SLOTS] = {};  // element size per field slot (0: slot unused)
+    uint8_t buf_elem[GHX_MAX_SLOTS] = {};   // per buffer slot (0: slot unused)
+    struct tables
+    {
+        void *tiles = nullptr, *srcs = nullptr;
+        tables() = default;
+        tables(const tables&) = delete;
+        tables& operator=(const tables&) = delete;
+        ~tables();
+    } dev;
+    saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, int n, const ghx_pack_entry* zero,
+                int n_zero);
+    int execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
+};
+
 // The per-call entry points' plans, cached by content (ghx_cache.cpp): the plan of the call's
 // descriptor and spaces, or index list, is built on first use and executed on `stream`.
 int run_structured(const ghx_field_desc& f, const ghx_box* boxes, int n, int dir, void* field,
@@ -325,4 +363,8 @@ struct ghx_uplan : ghx::uplan
 struct ghx_uaccum : ghx::uaccum_plan
 {
     using ghx::uaccum_plan::uaccum_plan;
+};
+struct ghx_saccum : ghx::saccum_plan
+{
+    using ghx::saccum_plan::saccum_plan;
 };

@@ -1,0 +1,406 @@
+// ghx_saccum_plan.cpp — the planner of the structured adjoint accumulate (saccum_plan, k_accum_s):
+// the arrangement of a field's overlapping contribution boxes into disjoint sub-boxes, each with
+// one list of sources, built on the host.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "ghx_plan.hpp"
+
+namespace ghx
+{
+namespace
+{
+bool have_device()
+{
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
+}
+
+int dtype_size(int32_t dt)
+{
+    switch (dt)
+    {
+        case GHX_DT_F32:
+        case GHX_DT_I32: return 4;
+        case GHX_DT_F64:
+        case GHX_DT_I64: return 8;
+        default: return 0;
+    }
+}
+
+int wlog2_of(uint64_t v) { return v ? std::min(4, __builtin_ctzll(v)) : 4; }
+
+template<typename T>
+void to_device(void*& to, const std::vector<T>& from, const char* what)
+{
+    if (from.empty()) return;
+    const size_t nb = from.size() * sizeof(T);
+    if (hipMalloc(&to, nb) != hipSuccess) throw hip_error(std::string("hipMalloc(") + what + ")");
+    if (hipMemcpy(to, from.data(), nb, hipMemcpyHostToDevice) != hipSuccess)
+        throw hip_error(std::string("hipMemcpy(") + what + ")");
+}
+
+bool same_field(const ghx_field_desc& a, const ghx_field_desc& b)
+{
+    bool same = a.dim == b.dim && a.elem_size == b.elem_size && a.num_components == b.num_components &&
+                (a.has_components != 0) == (b.has_components != 0);
+    for (int d = 0; same && d < a.dim; ++d)
+        same = a.layout[d] == b.layout[d] && a.byte_strides[d] == b.byte_strides[d] &&
+               a.offsets[d] == b.offsets[d] && a.extents[d] == b.extents[d];
+    return same;
+}
+
+// one box of an entry: its spatial bounds, where its dense buffer box starts and the buffer byte
+// stride of every field dim in it (layout order, component axis included: ghx_plan.cpp,
+// add_box_segments)
+struct cbox
+{
+    uint32_t entry, box;
+    int64_t first[GHX_MAX_DIM], last[GHX_MAX_DIM];
+    int32_t buf_slot;
+    uint64_t buf_off;
+    uint64_t bstride[GHX_MAX_DIM];
+};
+
+struct slot_boxes
+{
+    const ghx_field_desc* desc = nullptr;
+    int32_t dtype = 0;
+    std::vector<cbox> sum, zero;
+};
+
+constexpr uint64_t kMaxRecords = 0xffffffffull;  // source and tile indices are 32-bit
+}  // namespace
+
+saccum_plan::tables::~tables()
+{
+    for (void* p : {tiles, srcs})
+        if (p) (void)hipFree(p);
+}
+
+saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, int n, const ghx_pack_entry* zero,
+                         int n_zero)
+{
+    std::map<int32_t, slot_boxes> slots;
+    auto add_entry = [&](const ghx_pack_entry& en, uint32_t e, bool is_zero) {
+        const ghx_field_desc& f = en.field;
+        validate_field(f);
+        if (en.field_slot < 0 || (!is_zero && en.buffer_slot < 0)) throw invalid("negative slot");
+        if (en.field_slot >= GHX_MAX_SLOTS || (!is_zero && en.buffer_slot >= GHX_MAX_SLOTS))
+            throw invalid("an accumulate plan takes at most 64 field and 64 buffer slots (one launch)");
+        if (en.n_boxes < 0 || (en.n_boxes > 0 && !en.boxes)) throw invalid("bad boxes");
+        for (int d = 0; d < f.dim; ++d)
+            if (f.byte_strides[d] % f.elem_size)
+                throw invalid("a byte stride of the field is not a multiple of the element size");
+        slot_boxes& sb = slots[en.field_slot];
+        if (sb.desc && !same_field(*sb.desc, f))
+            throw invalid("two entries of field slot " + std::to_string(en.field_slot) +
+                          " differ in their field descriptor");
+        sb.desc = &f;
+        slot_elem[en.field_slot] = uint8_t(f.elem_size);
+        max_field_slot = std::max(max_field_slot, en.field_slot);
+        const int D = f.dim, spatial = D - (f.has_components ? 1 : 0);
+        int by_speed[GHX_MAX_DIM];
+        for (int d = 0; d < D; ++d) by_speed[D - 1 - f.layout[d]] = d;
+        uint64_t off = en.buffer_offset;
+        for (int b = 0; b < en.n_boxes; ++b)
+        {
+            cbox c{};
+            c.entry = e;
+            c.box = uint32_t(b);
+            c.buf_slot = en.buffer_slot;
+            c.buf_off = off;
+            int64_t ext[GHX_MAX_DIM];
+            for (int d = 0; d < D; ++d)
+            {
+                c.first[d] = d < spatial ? en.boxes[b].first[d] : 0;
+                c.last[d] = d < spatial ? en.boxes[b].last[d] : f.num_components - 1;
+                ext[d] = c.last[d] - c.first[d] + 1;
+                if (ext[d] <= 0) throw invalid("iteration space: first must be <= last");
+                // the rule of ghx_plan_create (add_box_segments)
+                const int64_t o = d < spatial ? f.offsets[d] : 0;
+                if (f.extents[d] > 0 && (c.first[d] + o < 0 || c.last[d] + o >= f.extents[d]))
+                    throw invalid("iteration space outside the field extents");
+            }
+            uint64_t bs = uint64_t(f.elem_size);
+            for (int k = 0; k < D; ++k)
+            {
+                c.bstride[by_speed[k]] = bs;
+                bs *= uint64_t(ext[by_speed[k]]);
+            }
+            off += bs;
+            (is_zero ? sb.zero : sb.sum).push_back(c);
+        }
+    };
+    for (int e = 0; e < n; ++e)
+    {
+        const ghx_pack_entry& en = contrib[e];
+        const int sz = dtype_size(dtypes[e]);
+        if (!sz) throw invalid("unknown dtype code " + std::to_string(dtypes[e]) + " (GHX_DT_F32, _F64, _I32, _I64)");
+        if (sz != en.field.elem_size)
+            throw invalid("dtype code " + std::to_string(dtypes[e]) + " has " + std::to_string(sz) +
+                          " bytes, the entry's elem_size is " + std::to_string(en.field.elem_size));
+        add_entry(en, uint32_t(e), false);
+        int32_t& dt = slots[en.field_slot].dtype;
+        if (dt && dt != dtypes[e])
+            throw invalid("two entries of field slot " + std::to_string(en.field_slot) + " differ in their dtype");
+        dt = dtypes[e];
+        if (en.buffer_offset % uint64_t(sz)) throw invalid("buffer offset is not a multiple of the element size");
+        max_buf_slot = std::max(max_buf_slot, en.buffer_slot);
+        buf_elem[en.buffer_slot] = std::max(buf_elem[en.buffer_slot], uint8_t(sz));
+    }
+    for (int k = 0; k < n_zero; ++k)
+    {
+        if (zero[k].field.elem_size != 4 && zero[k].field.elem_size != 8)
+            throw invalid("a zero entry's elem_size is " + std::to_string(zero[k].field.elem_size) +
+                          ", not that of a dtype (4 or 8)");
+        add_entry(zero[k], uint32_t(k), true);
+    }
+    // no cell is both summed and zeroed: box against box
+    for (const auto& kv : slots)
+    {
+        const int spatial = kv.second.desc->dim - (kv.second.desc->has_components ? 1 : 0);
+        for (const cbox& a : kv.second.sum)
+            for (const cbox& z : kv.second.zero)
+            {
+                bool meet = true;
+                for (int d = 0; meet && d < spatial; ++d) meet = a.first[d] <= z.last[d] && z.first[d] <= a.last[d];
+                if (meet)
+                    throw invalid("a cell of field slot " + std::to_string(kv.first) + " is both summed and zeroed (box " +
+                                  std::to_string(a.box) + " of contribution entry " + std::to_string(a.entry) +
+                                  " meets box " + std::to_string(z.box) + " of zero entry " + std::to_string(z.entry) + ")");
+            }
+    }
+
+    const uint32_t tb = std::max<uint32_t>(1, g_tune.tile_bytes);
+    // one sub-box (spatial bounds first / last, sources `list` into `from`) -> box, source and
+    // tile records
+    auto emit = [&](int32_t slot, const slot_boxes& sb, const int64_t* first, const int64_t* last,
+                    const std::vector<cbox>& from, const std::vector<uint32_t>& list, bool is_zero) {
+        const ghx_field_desc& f = *sb.desc;
+        const int D = f.dim, spatial = D - (f.has_components ? 1 : 0);
+        const int64_t elem = f.elem_size;
+        int by_speed[GHX_MAX_DIM];
+        for (int d = 0; d < D; ++d) by_speed[D - 1 - f.layout[d]] = d;
+        int64_t ext[GHX_MAX_DIM], lo[GHX_MAX_DIM];
+        for (int d = 0; d < D; ++d)
+        {
+            lo[d] = d < spatial ? first[d] : 0;
+            ext[d] = d < spatial ? last[d] - first[d] + 1 : f.num_components;
+        }
+        if (uint64_t(srcs.size()) + list.size() > kMaxRecords) throw invalid("more than 2^32 - 1 source records");
+        const uint32_t first_src = uint32_t(srcs.size());
+        // rows along the layout's fastest dim; a strided fastest dim makes every element a row
+        const int cont = by_speed[0];
+        const bool unit = f.byte_strides[cont] == elem;
+        int64_t L = unit ? ext[cont] * elem : elem;
+        int outer[GHX_MAX_DIM];
+        int n_outer = 0;
+        for (int k = unit ? 1 : 0; k < D; ++k)
+            if (ext[by_speed[k]] > 1) outer[n_outer++] = by_speed[k];
+        // rows that are adjacent in the field and in every source's buffer box are one row
+        auto mergeable = [&] {
+            if (n_outer == 0 || f.byte_strides[outer[0]] != L || L * ext[outer[0]] >= (int64_t(1) << 30)) return false;
+            for (uint32_t j : list)
+                if (from[j].bstride[outer[0]] != uint64_t(L)) return false;
+            return true;
+        };
+        while (mergeable())
+        {
+            L *= ext[outer[0]];
+            for (int k = 1; k < n_outer; ++k) outer[k - 1] = outer[k];
+            --n_outer;
+        }
+        if (L >= (int64_t(1) << 31)) throw invalid("row too long");
+        sacc_tile t{};
+        uint64_t rows = 1;
+        int w = wlog2_of(uint64_t(L));
+        for (int d = 0; d < D; ++d) t.field_off += (lo[d] + (d < spatial ? f.offsets[d] : 0)) * f.byte_strides[d];
+        w = std::min(w, wlog2_of(uint64_t(t.field_off)));
+        for (int k = 0; k < 4; ++k)
+        {
+            t.stride[k] = k < n_outer ? f.byte_strides[outer[k]] : 0;
+            t.ext[k] = k < n_outer ? uint32_t(ext[outer[k]]) : 1;
+            rows *= t.ext[k];
+            if (k < n_outer) w = std::min(w, wlog2_of(uint64_t(t.stride[k])));
+        }
+        if (rows > kMaxRecords) throw invalid("a sub-box has more than 2^32 - 1 rows");
+        for (uint32_t j : list)
+        {
+            const cbox& c = from[j];
+            sacc_src s{};
+            s.buf_off = c.buf_off;
+            for (int d = 0; d < spatial; ++d) s.buf_off += uint64_t(lo[d] - c.first[d]) * c.bstride[d];
+            s.buf_slot = uint32_t(c.buf_slot);
+            w = std::min(w, wlog2_of(s.buf_off));
+            for (int k = 0; k < n_outer; ++k)
+            {
+                s.stride[k] = c.bstride[outer[k]];
+                w = std::min(w, wlog2_of(s.stride[k]));
+            }
+            t.buf_mask |= uint64_t(1) << c.buf_slot;
+            srcs.push_back(s);
+            src_entry.push_back(c.entry);
+            src_box.push_back(c.box);
+        }
+        for (int k = 0; k < 3; ++k) t.mag_ext[k] = make_magic(t.ext[k]);
+        t.first_src = first_src;
+        t.n_src = uint32_t(list.size());
+        t.field_slot = uint16_t(slot);
+        t.zero = is_zero ? 1 : 0;
+        t.dtype = uint8_t(is_zero ? (elem == 8 ? GHX_DT_I64 : GHX_DT_I32) : sb.dtype);
+        t.wlog2 = uint8_t(w);
+        t.n_outer = uint8_t(n_outer);
+        saccum_box bx{};
+        bx.field_slot = slot;
+        bx.zero = is_zero;
+        for (int d = 0; d < spatial; ++d)
+        {
+            bx.first[d] = int32_t(first[d]);
+            bx.last[d] = int32_t(last[d]);
+        }
+        bx.row_elems = uint64_t(L / elem);
+        bx.wlog2 = uint8_t(w);
+        bx.first_src = first_src;
+        bx.n_src = t.n_src;
+        boxes.push_back(bx);
+        max_sources = std::max(max_sources, t.n_src);
+        bytes += rows * uint64_t(L) * list.size();
+        // tiles: whole rows of tile_bytes field bytes; a row longer than that in pieces
+        auto push = [&](uint32_t row, uint32_t nr, uint32_t col0, uint32_t len) {
+            if (tiles.size() >= kMaxRecords) throw invalid("more than 2^32 - 1 tiles");
+            t.first_row = row;
+            t.n_rows = nr;
+            t.col0 = col0;
+            t.len = len;
+            t.mag_vec = make_magic(len >> w);
+            tiles.push_back(t);
+        };
+        if (uint64_t(L) > tb)
+        {
+            const uint32_t piece = std::max<uint32_t>(16, tb - tb % 16);
+            for (uint64_t r = 0; r < rows; ++r)
+                for (uint32_t c0 = 0; c0 < uint32_t(L); c0 += piece)
+                    push(uint32_t(r), 1, c0, std::min(piece, uint32_t(L) - c0));
+        }
+        else
+        {
+            const uint64_t per = std::max<uint64_t>(1, tb / uint64_t(L));
+            for (uint64_t r = 0; r < rows; r += per) push(uint32_t(r), uint32_t(std::min(per, rows - r)), 0, uint32_t(L));
+        }
+    };
+
+    // the arrangement, per field slot: every dimension cut at every box's first and last + 1; an
+    // elementary box lies in a contribution box or outside it. Boxes come in ascending (entry,
+    // box), so every list ascends. Elementary boxes adjacent along the fastest spatial dimension
+    // with equal lists are merged.
+    for (const auto& kv : slots)
+    {
+        const slot_boxes& sb = kv.second;
+        if (sb.sum.empty()) continue;
+        const ghx_field_desc& f = *sb.desc;
+        const int spatial = f.dim - (f.has_components ? 1 : 0);
+        int order[GHX_MAX_DIM];  // spatial dims, slowest first
+        int no = 0;
+        for (int l = 0; l < f.dim; ++l)
+            for (int d = 0; d < spatial; ++d)
+                if (f.layout[d] == l) order[no++] = d;
+        std::vector<int64_t> cuts[GHX_MAX_DIM];
+        for (int d = 0; d < spatial; ++d)
+        {
+            for (const cbox& c : sb.sum)
+            {
+                cuts[d].push_back(c.first[d]);
+                cuts[d].push_back(c.last[d] + 1);
+            }
+            std::sort(cuts[d].begin(), cuts[d].end());
+            cuts[d].erase(std::unique(cuts[d].begin(), cuts[d].end()), cuts[d].end());
+        }
+        using key = std::array<uint32_t, GHX_MAX_DIM>;  // interval index per dim of `order`
+        std::map<key, std::vector<uint32_t>> cells;
+        for (uint32_t j = 0; j < sb.sum.size(); ++j)
+        {
+            const cbox& c = sb.sum[j];
+            uint32_t lo[GHX_MAX_DIM] = {}, hi[GHX_MAX_DIM] = {1, 1, 1, 1};
+            for (int k = 0; k < spatial; ++k)
+            {
+                const std::vector<int64_t>& cu = cuts[order[k]];
+                lo[k] = uint32_t(std::lower_bound(cu.begin(), cu.end(), c.first[order[k]]) - cu.begin());
+                hi[k] = uint32_t(std::lower_bound(cu.begin(), cu.end(), c.last[order[k]] + 1) - cu.begin());
+            }
+            key i{};
+            for (i[0] = lo[0]; i[0] < hi[0]; ++i[0])
+                for (i[1] = lo[1]; i[1] < hi[1]; ++i[1])
+                    for (i[2] = lo[2]; i[2] < hi[2]; ++i[2])
+                        for (i[3] = lo[3]; i[3] < hi[3]; ++i[3]) cells[i].push_back(j);
+        }
+        const int fast = spatial - 1;  // position in `order` of the fastest spatial dim
+        auto it = cells.begin();
+        while (it != cells.end())
+        {
+            key a = it->first;
+            uint32_t end = a[fast] + 1;
+            auto nx = std::next(it);
+            for (; nx != cells.end(); ++nx, ++end)
+            {
+                key b = nx->first;
+                const bool follows = b[fast] == end;
+                b[fast] = a[fast];
+                if (!follows || b != a || nx->second != it->second) break;
+            }
+            int64_t first[GHX_MAX_DIM] = {}, last[GHX_MAX_DIM] = {};
+            for (int k = 0; k < spatial; ++k)
+            {
+                first[order[k]] = cuts[order[k]][a[k]];
+                last[order[k]] = cuts[order[k]][(k == fast ? end : a[k] + 1)] - 1;
+            }
+            emit(kv.first, sb, first, last, sb.sum, it->second, false);
+            it = nx;
+        }
+    }
+    n_sum_boxes = uint32_t(boxes.size());
+    n_sum_tiles = uint32_t(tiles.size());
+    for (const auto& kv : slots)
+        for (const cbox& z : kv.second.zero) emit(kv.first, kv.second, z.first, z.last, kv.second.zero, {}, true);
+
+    if (tiles.empty() || !have_device()) return;
+    to_device(dev.tiles, tiles, "accumulate tiles");
+    to_device(dev.srcs, srcs, "accumulate sources");
+}
+
+int saccum_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const
+{
+    const uint32_t n_tiles = zero_halos ? uint32_t(tiles.size()) : n_sum_tiles;
+    if (n_tiles == 0) return GHX_OK;
+    if (!fptr || (!bptr && max_buf_slot >= 0) || nf <= max_field_slot || nb <= max_buf_slot)
+        throw invalid("pointer arrays do not cover the plan's slots");
+    kargs_sa a{};
+    a.n_tiles = n_tiles;
+    for (int s = 0; s <= max_field_slot; ++s)
+    {
+        if (!slot_elem[s]) continue;
+        if (!fptr[s]) throw invalid("null field pointer");
+        a.field_ptr[s] = reinterpret_cast<uint64_t>(fptr[s]);
+        if (a.field_ptr[s] % slot_elem[s]) throw invalid("a field pointer is not aligned to its element");
+    }
+    for (int b = 0; b <= max_buf_slot; ++b)
+    {
+        if (!buf_elem[b]) continue;
+        if (!bptr[b]) throw invalid("null buffer pointer");
+        a.buf_ptr[b] = reinterpret_cast<uint64_t>(bptr[b]);
+        if (a.buf_ptr[b] % buf_elem[b]) throw invalid("a buffer pointer is not aligned to its elements");
+        if (a.buf_ptr[b] % 8) a.buf_mis8 |= uint64_t(1) << b;
+        if (a.buf_ptr[b] % 16) a.buf_mis16 |= uint64_t(1) << b;
+    }
+    if (!dev.tiles) throw hip_error("plan has no device tables (no HIP device at creation)");
+    a.tiles = static_cast<const sacc_tile*>(dev.tiles);
+    a.srcs = static_cast<const sacc_src*>(dev.srcs);
+    return launch_accum_s(a, stream, grid_for_tiles(n_tiles));
+}
+
+}  // namespace ghx

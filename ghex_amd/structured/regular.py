@@ -274,6 +274,18 @@ class FieldDescriptor:
     def domain_id(self) -> int:
         return self.domain.domain_id()
 
+    def dtype_code(self) -> int:
+        """The element type code of the adjoint exchange (GHX_DT_*): the only operation that
+        computes with the elements. TypeError for a dtype it does not sum."""
+        import torch
+        codes = {torch.float32: _ghx.DT_F32, torch.float64: _ghx.DT_F64,
+                 torch.int32: _ghx.DT_I32, torch.int64: _ghx.DT_I64}
+        code = codes.get(self.tensor.dtype)
+        if code is None:
+            raise TypeError(f"adjoint exchange: dtype {self.tensor.dtype} is not supported "
+                            "(float32, float64, int32, int64)")
+        return code
+
     def data_ptr(self) -> int:
         return self.tensor.data_ptr()
 

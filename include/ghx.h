@@ -967,6 +967,91 @@ int ghx_uexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_
                                      int32_t n_fields, void* const* send_buffers, int32_t n_send,
                                      int32_t zero_halos, ghx_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Adjoint halo exchange of structured fields (no reference counterpart): the operation above with
+ * boxes in place of lists. Message m of an exchange pairs box k of a send entry with box k of the
+ * peer's receive entry (equal extents) and copies R[recv cell] = S[send cell] cell by cell in
+ * buffer order; its adjoint does S[send cell] += R[recv cell] for every message, box and cell
+ * (component axis included) and then, with zero_halos, stores zero bytes to every receive-box
+ * cell. Two launches around the transport: a reverse pack (a ghx_plan of direction 0 over the
+ * RECEIVE entries) and the accumulate below (k_accum_s), which reads the SEND buffers.
+ * A field's send boxes overlap (a corner cell of a periodic domain lies in 7 of them, every cell
+ * of a domain narrower than its halo in up to 26). The planner cuts, per field slot, the union of
+ * the contribution boxes into disjoint sub-boxes — every dimension at every box's first and
+ * last + 1, elementary boxes no box holds dropped, neighbours along the fastest spatial dimension
+ * with equal source lists merged — so every cell of a sub-box has the same sources: the boxes
+ * that hold it, in ascending (entry, box). A destination cell starts from its own value and adds
+ * its contributions one at a time in that order, in the element type, without reassociation or
+ * contraction; integers as unsigned (they wrap). Bitwise reproducible, no atomics.
+ *
+ * contrib[e], e < n, are ghx_pack_entry as the pack entries of an exchange (the buffer position of
+ * a box cell is the one ghx_plan_create gives it: boxes one after the other from buffer_offset,
+ * each dense in layout order with the component axis); dtypes[e] the GHX_DT_* code of entry e.
+ * zero[k] name the halo side (field slot, descriptor and boxes; buffer members ignored): their
+ * boxes become zero sub-boxes without sources. Tiles: the rows of one sub-box (runs along the
+ * layout's fastest dimension; single elements where that dimension is strided) cut by the
+ * "tile_bytes" knob in field bytes, sum tiles first, so a launch without zero_halos runs those
+ * only. One launch, stream-ordered, never allocates, can be captured.
+ * GHX_ERR_INVALID, with the reason in ghx_last_error(), when: a dtype code is unknown or its size
+ * differs from the entry's elem_size; a zero entry's elem_size is not 4 or 8; a field or buffer
+ * slot is negative or >= 64 (one launch, no launch groups); two entries of one field slot differ
+ * in their field descriptor or dtype; a byte stride of a field is no multiple of its element;
+ * buffer_offset is no multiple of the element size; a cell is both summed and zeroed; a box lies
+ * outside the field's extents (ghx_plan_create's rule) or has first > last; the plan would hold
+ * more than 2^32 - 1 source records. Overlapping buffer ranges are accepted: contributions are
+ * only read. Execution refuses pointer arrays that do not cover the plan's slots and pointers
+ * that are not aligned to the element.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ghx_saccum ghx_saccum;
+int ghx_saccum_create(const ghx_pack_entry* contrib, const int32_t* dtypes, int32_t n,
+                      const ghx_pack_entry* zero, int32_t n_zero, ghx_saccum** out);
+int ghx_saccum_execute(const ghx_saccum* p, void* const* field_ptrs, int32_t n_fields,
+                       void* const* buffer_ptrs, int32_t n_buffers, int32_t zero_halos,
+                       ghx_stream stream);
+/* buffer bytes read per execution, sum sub-boxes, zero sub-boxes, source records, the longest
+ * source list, workgroup tiles (sum and zero tiles) */
+int ghx_saccum_info(const ghx_saccum* p, uint64_t* bytes, int64_t* n_boxes, int64_t* n_zero_boxes,
+                    int64_t* n_sources, int64_t* max_sources, int32_t* n_tiles);
+/* Sub-box k of the plan (host only), k in [0, n_boxes + n_zero_boxes): its bounds in the field's
+ * local coordinates (spatial dims), the length of its rows in elements, the planned vector width
+ * and, for a sum sub-box, its records [first_src, first_src + n_src) of ghx_saccum_source; a zero
+ * sub-box has zero = 1 and no records. */
+typedef struct ghx_saccum_box_info
+{
+    int32_t field_slot;
+    int32_t zero;
+    int32_t first[GHX_MAX_DIM];
+    int32_t last[GHX_MAX_DIM];
+    int64_t row_elems;
+    int32_t wlog2;
+    int32_t pad;
+    int64_t first_src;
+    int64_t n_src;
+} ghx_saccum_box_info;
+int ghx_saccum_box(const ghx_saccum* p, int64_t k, ghx_saccum_box_info* out);
+/* Source record j in [0, n_sources): the contribution entry and its box, the buffer slot and the
+ * byte offset in that buffer of the cell at the sub-box's origin (component 0). */
+int ghx_saccum_source(const ghx_saccum* p, int64_t j, int32_t* entry, int32_t* box,
+                      int32_t* buffer_slot, uint64_t* buffer_offset_of_origin);
+int ghx_saccum_destroy(ghx_saccum* p);
+
+/* The adjoint of an exchange of regular structured items, the twin of ghx_uexchange_adjoint_*:
+ * create attaches the reverse pack (a ghx_plan of direction 0 over the exchange's unpack entries)
+ * and the accumulate plan (pack entries as contribution entries, unpack entries as zero entries);
+ * dtypes[i] is the GHX_DT_* code of item i. GHX_ERR_INVALID, with the reason, for an exchange that
+ * holds an unstructured or a cubed-sphere item, while a direction has parity set, and for
+ * ghx_saccum_create's reasons. info works on any exchange. pack has ghx_exchange_unpack's argument
+ * contract (it writes the RECEIVE buffers), accumulate ghx_exchange_pack's (it reads the SEND
+ * buffers); both fail with GHX_ERR_INVALID before create and while a direction has parity set. */
+int ghx_sexchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items);
+int ghx_sexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_boxes,
+                               int64_t* n_sources);
+int ghx_sexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                               void* const* recv_buffers, int32_t n_recv, ghx_stream stream);
+int ghx_sexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
+                                     int32_t n_fields, void* const* send_buffers, int32_t n_send,
+                                     int32_t zero_halos, ghx_stream stream);
+
 /* Device-side access epochs of the zero-copy exchanges (bulk puts, direct pack): the reference's
  * access guards (include/ghex/rma/access_guard.hpp:35-140; per range: start/end_target_epoch on
  * the owner, start/end_source_epoch on the putter; include/ghex/bulk_communication_object.hpp
