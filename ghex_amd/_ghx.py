@@ -180,8 +180,16 @@ _SIGS = {
     "ghx_sexchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64)]),
     "ghx_sexchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_sexchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
+    "ghx_cs_exchange_adjoint_create": (c_i32, [c_vp, P(c_i32), c_i32]),
+    "ghx_cs_exchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i32), P(c_i32)]),
+    "ghx_cs_exchange_adjoint_plan": (c_i32, [c_vp, P(c_vp)]),
+    "ghx_cs_exchange_adjoint_segments": (c_i32, [c_vp, P(c_i32), P(c_i32)]),
+    "ghx_cs_exchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_cs_exchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
                               c_i32, c_vp]),
+    "ghx_cs_pack_rotated": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
+                                    c_i32, c_vp]),
     "ghx_udomain_create": (c_i32, [c_i32, P(c_i64), c_i64, P(c_i64), c_i64, P(c_vp)]),
     "ghx_udomain_destroy": (c_i32, [c_vp]),
     "ghx_udomain_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i64)]),

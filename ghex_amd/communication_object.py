@@ -253,7 +253,7 @@ class CommunicationObject:
                  rccl_self: bool = False, max_streams: int = 4, copy_engine: str = "probe",
                  direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False,
                  fuse_lists: bool = False, fuse_lists_mixed: bool = False,
-                 adjoint_boxes: bool = False):
+                 adjoint_boxes: bool = False, adjoint_rotated: bool = False):
         if staging not in (None, "host"):
             raise ValueError("staging must be None (device buffers) or 'host'")
         if direct and (staging is not None or pipelined or rccl_self):
@@ -288,6 +288,10 @@ class CommunicationObject:
         # summed through an arrangement of sub-boxes (ghx_sexchange_adjoint_*, k_accum_s). Opt-in;
         # without it the adjoint exchange takes unstructured fields only, as before
         self.adjoint_boxes = bool(adjoint_boxes)
+        # cubed-sphere fields in the adjoint exchange: the reverse pack rotates and negates as the
+        # unpack does (ghx_cs_exchange_adjoint_*, k_pack_x), the accumulate is k_accum_s. Opt-in;
+        # without it a cubed-sphere field is refused, as before
+        self.adjoint_rotated = bool(adjoint_rotated)
         self.staging = staging
         self.pipelined = pipelined
         # tests: route the self messages through RCCL too (a 1-rank communicator), so the
@@ -574,10 +578,17 @@ class CommunicationObject:
     def _adjoint_plan(self, bis):
         """The plan of `bis` with its adjoint plans attached (built on first use): the reverse
         pack and the accumulate (ghx_uexchange_adjoint_create, k_accum_u; with adjoint_boxes and
-        regular structured fields ghx_sexchange_adjoint_create, k_accum_s)."""
+        regular structured fields ghx_sexchange_adjoint_create, k_accum_s; with adjoint_rotated
+        and cubed-sphere fields ghx_cs_exchange_adjoint_create, k_pack_x and k_accum_s)."""
         if self.direct or self.pipelined:
             raise ValueError("the adjoint exchange is the plain communication object's "
                              "(no direct=True, no pipelined=True)")
+        rotated = [getattr(bi.field, "cs_item", None) is not None for bi in bis]
+        if self.adjoint_rotated and any(rotated):
+            if not all(rotated):
+                raise ValueError("an exchange takes cubed-sphere fields or other fields, "
+                                 "not both")
+            return self._with_adjoint(bis, "ghx_cs_exchange_adjoint_")
         boxes = self.adjoint_boxes and any(
             bi.field.kind != 1 or getattr(bi.field, "cs_item", None) is not None for bi in bis)
         for bi in bis:
@@ -591,11 +602,13 @@ class CommunicationObject:
             if not boxes and (bi.field.kind != 1 or cs):
                 raise ValueError("the adjoint exchange takes unstructured fields only (structured "
                                  "and cubed-sphere send boxes overlap)")
+        # boxes: ghx_sexchange_adjoint_* (k_accum_s), lists: ghx_uexchange_adjoint_* (k_accum_u)
+        return self._with_adjoint(bis, "ghx_sexchange_adjoint_" if boxes else "ghx_uexchange_adjoint_")
+
+    def _with_adjoint(self, bis, prefix):
         codes = [bi.field.dtype_code() for bi in bis]  # TypeError for any other dtype
         plan = self.plan(bis)
         if getattr(plan, "_adjoint_codes", None) != codes:
-            # boxes: ghx_sexchange_adjoint_* (k_accum_s), lists: ghx_uexchange_adjoint_* (k_accum_u)
-            prefix = "ghx_sexchange_adjoint_" if boxes else "ghx_uexchange_adjoint_"
             _ghx.call(prefix + "create", plan.h, _ghx.i32_array(codes), len(codes))
             plan._adjoint_codes = codes
             plan._adjoint_prefix = prefix
@@ -603,8 +616,9 @@ class CommunicationObject:
 
     def adjoint_exchange(self, *buffer_infos, zero_halos: bool = True) -> CommunicationHandle:
         """The transpose of exchange() for unstructured fields and, on an object made with
-        adjoint_boxes=True, for regular structured fields, non-blocking on the current
-        stream: every halo cell's value is sent back to the cell's owner and added to it, in a
+        adjoint_boxes=True, for regular structured fields, or with adjoint_rotated=True for
+        cubed-sphere fields, non-blocking on the current stream: every halo cell's value is sent
+        back to the cell's owner and added to it, in a
         fixed order (bitwise reproducible, no atomics); with zero_halos the halo cells are then
         set to zero (the true transpose), without it they keep their values (assembly). The plain
         path: reverse pack into the receive buffers, the forward transport with the roles

@@ -504,6 +504,20 @@ int ghx_cs_unpack(const ghx_field_desc* field, const ghx_cs_item* cs, void* fiel
     });
 }
 
+int ghx_cs_pack_rotated(const ghx_field_desc* field, const ghx_cs_item* cs, const void* field_data,
+                        void* buffer, const ghx_box* local, const ghx_box* global,
+                        const int32_t* tiles, int32_t n_boxes, ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(field, "field");
+        check_ptr(cs, "cs");
+        if (n_boxes < 0 || (n_boxes > 0 && (!local || !global || !tiles))) throw invalid("bad boxes");
+        check_cs_item(*field, *cs);
+        if (n_boxes == 0) return int(GHX_OK);
+        return run_cs_pack_rotated(*field, *cs, local, global, tiles, n_boxes, field_data, buffer, stream);
+    });
+}
+
 int ghx_pattern_filter(const ghx_pattern* p, const int32_t* ranks, int32_t n_ranks, int32_t keep,
                        ghx_pattern** out)
 {
@@ -1471,6 +1485,92 @@ int ghx_sexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_
         check_sadjoint(ex);
         if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
         return ex->sadj_accum->execute(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
+    });
+}
+
+int ghx_cs_exchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        ex->make_cs_adjoint(dtypes, n_items);
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_exchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_boxes, int64_t* n_sources,
+                                 int32_t* n_pack_x_records, int32_t* n_pack_x_tiles)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(ready, "ready");
+        const saccum_plan* p = ex->cs_adj_ready ? ex->cs_adj_accum.get() : nullptr;
+        *ready = p ? 1 : 0;
+        if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
+        if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
+        if (n_pack_x_records) *n_pack_x_records = p && ex->xunpack ? ex->xunpack->n_records : 0;
+        if (n_pack_x_tiles) *n_pack_x_tiles = p && ex->xunpack ? int32_t(ex->xunpack->n_tiles) : 0;
+        return GHX_OK;
+    });
+}
+
+namespace
+{
+void check_cs_adjoint(const ghx_exchange* ex)
+{
+    check_ptr(ex, "exchange");
+    if (!ex->cs_adj_ready)
+        throw invalid("cubed-sphere adjoint exchange: no adjoint plans (ghx_cs_exchange_adjoint_create)");
+    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+}
+}  // namespace
+
+int ghx_cs_exchange_adjoint_plan(const ghx_exchange* ex, const ghx_saccum** out)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(out, "out");
+        if (!ex->cs_adj_ready)
+            throw invalid("cubed-sphere adjoint exchange: no adjoint plans (ghx_cs_exchange_adjoint_create)");
+        *out = ex->cs_adj_accum.get();
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_exchange_adjoint_segments(const ghx_exchange* ex, int32_t* n_pack_segments, int32_t* n_unpack_segments)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        if (n_pack_segments) *n_pack_segments = ex->cs_adj_pack ? ex->cs_adj_pack->n_segments : 0;
+        if (n_unpack_segments) *n_unpack_segments = ex->cubed_sphere && ex->sunpack ? ex->sunpack->n_segments : 0;
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_exchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                 void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
+{
+    return guarded([&] {
+        check_cs_adjoint(ex);
+        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
+        int rc = GHX_OK;
+        if (ex->cs_adj_pack) rc = ex->cs_adj_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+        // the transformed spaces, after the ordinary launch on the same stream
+        if (rc == GHX_OK && ex->xunpack)
+            rc = ex->xunpack->execute_pack(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+        return rc;
+    });
+}
+
+int ghx_cs_exchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                       void* const* send_buffers, int32_t n_send, int32_t zero_halos,
+                                       ghx_stream stream)
+{
+    return guarded([&] {
+        check_cs_adjoint(ex);
+        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
+        return ex->cs_adj_accum->execute(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
     });
 }
 

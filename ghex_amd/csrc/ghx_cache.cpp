@@ -168,9 +168,10 @@ plan_lru<uplan>& ucache()
 }
 
 // ghx_cs_unpack's cached plan: the ordinary and the transformed part of one field's spaces
+// (sp: the ordinary part once more as a pack plan, for ghx_cs_pack_rotated; x serves both ways)
 struct cs_field_plan
 {
-    std::unique_ptr<splan> s;
+    std::unique_ptr<splan> s, sp;
     std::unique_ptr<xplan> x;
 };
 
@@ -205,16 +206,18 @@ int run_structured(const ghx_field_desc& f, const ghx_box* boxes, int n, int dir
     return rc;
 }
 
-int run_cs_unpack(const ghx_field_desc& f, const ghx_cs_item& cs, const ghx_box* local,
-                  const ghx_box* global, const int32_t* tiles, int n, void* field, void* buffer,
-                  void* stream)
+namespace
+{
+std::shared_ptr<cached_plan<cs_field_plan>> cs_field_plan_of(const ghx_field_desc& f, const ghx_cs_item& cs,
+                                                             const ghx_box* local, const ghx_box* global,
+                                                             const int32_t* tiles, int n)
 {
     std::string key(reinterpret_cast<const char*>(&f), sizeof(f));
     key.append(reinterpret_cast<const char*>(&cs), sizeof(cs));
     key.append(reinterpret_cast<const char*>(local), sizeof(ghx_box) * size_t(n));
     key.append(reinterpret_cast<const char*>(global), sizeof(ghx_box) * size_t(n));
     key.append(reinterpret_cast<const char*>(tiles), sizeof(int32_t) * size_t(n));
-    auto c = cs_cache().get(
+    return cs_cache().get(
         key, [](const cached_plan<cs_field_plan>&) { return true; },
         [&] {
             cs_recv_plan rp;
@@ -236,15 +239,40 @@ int run_cs_unpack(const ghx_field_desc& f, const ghx_cs_item& cs, const ghx_box*
             auto p = std::make_shared<cached_plan<cs_field_plan>>();
             p->plan = std::make_unique<cs_field_plan>();
             if (!rp.segs.empty())
+            {
+                p->plan->sp = std::make_unique<splan>(rp.segs, rp.gf, rp.gb, rp.sbytes, 0);
                 p->plan->s = std::make_unique<splan>(std::move(rp.segs), rp.gf, rp.gb, rp.sbytes, 1);
+            }
             if (!rp.xs.empty()) p->plan->x = std::make_unique<xplan>(std::move(rp.xs));
             return p;
         });
+}
+}  // namespace
+
+int run_cs_unpack(const ghx_field_desc& f, const ghx_cs_item& cs, const ghx_box* local,
+                  const ghx_box* global, const int32_t* tiles, int n, void* field, void* buffer,
+                  void* stream)
+{
+    auto c = cs_field_plan_of(f, cs, local, global, tiles, n);
     void* fp[1] = {field};
     void* bp[1] = {buffer};
     int rc = GHX_OK;
     if (c->plan->s) rc = c->plan->s->execute(fp, 1, bp, 1, stream);
     if (rc == GHX_OK && c->plan->x) rc = c->plan->x->execute(fp, 1, bp, 1, stream);
+    cs_cache().used(*c, stream);
+    return rc;
+}
+
+int run_cs_pack_rotated(const ghx_field_desc& f, const ghx_cs_item& cs, const ghx_box* local,
+                        const ghx_box* global, const int32_t* tiles, int n, const void* field,
+                        void* buffer, void* stream)
+{
+    auto c = cs_field_plan_of(f, cs, local, global, tiles, n);
+    void* fp[1] = {const_cast<void*>(field)};
+    void* bp[1] = {buffer};
+    int rc = GHX_OK;
+    if (c->plan->sp) rc = c->plan->sp->execute(fp, 1, bp, 1, stream);
+    if (rc == GHX_OK && c->plan->x) rc = c->plan->x->execute_pack(fp, 1, bp, 1, stream);
     cs_cache().used(*c, stream);
     return rc;
 }

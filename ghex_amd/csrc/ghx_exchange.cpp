@@ -671,6 +671,12 @@ std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, cons
         ex->only_structured = ex->only_structured && items[i].kind == 0;
     }
     ex->cubed_sphere = cs != nullptr;
+    if (cs)
+        for (int32_t i = 0; i < n_items; ++i)
+        {
+            ex->cs_items.push_back(cs[i]);
+            ex->cs_elem.push_back(items[i].field.elem_size);
+        }
     std::vector<ghx_pack_entry> rent;              // receive entries, for build_mixed
     std::vector<const halo_entry*> rhalos;         // and their halo entries, for build_cs_self
     for (int dir = 0; dir < 2; ++dir)
@@ -709,6 +715,10 @@ std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, cons
                 }
             }
             ex->cs_rotated = rp.n_rotated;
+            ex->cs_segs = rp.segs;  // for the reverse pack (make_cs_adjoint)
+            ex->cs_gf = rp.gf;
+            ex->cs_gb = rp.gb;
+            ex->cs_sbytes = rp.sbytes;
             if (!rp.segs.empty())
                 ex->sunpack = std::make_unique<splan>(std::move(rp.segs), rp.gf, rp.gb, rp.sbytes, 1);
             if (!rp.xs.empty()) ex->xunpack = std::make_unique<xplan>(std::move(rp.xs));
@@ -824,6 +834,42 @@ void exchange_plan::make_sadjoint(const int32_t* dtypes, int32_t n)
     auto pack = std::make_unique<splan>(entries[1].data(), int(entries[1].size()), 0);
     sadj_accum = std::move(accum);
     sadj_pack = std::move(pack);
+}
+
+void exchange_plan::make_cs_adjoint(const int32_t* dtypes, int32_t n)
+{
+    if (!cubed_sphere)
+        throw invalid("cubed-sphere adjoint exchange: not a cubed-sphere exchange (regular structured items take "
+                      "ghx_sexchange_adjoint_create, index-list items ghx_uexchange_adjoint_create)");
+    if (dir_parity[0].word || dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+    if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
+    for (int32_t i = 0; i < n; ++i)
+    {
+        if (dtypes[i] < GHX_DT_F32 || dtypes[i] > GHX_DT_I64)
+            throw invalid("unknown dtype code " + std::to_string(dtypes[i]) + " (GHX_DT_F32, _F64, _I32, _I64)");
+        // a receive-only item names no contribution entry: its size is checked here
+        const int32_t size = (dtypes[i] == GHX_DT_F32 || dtypes[i] == GHX_DT_I32) ? 4 : 8;
+        if (size != cs_elem[size_t(i)])
+            throw invalid("cubed-sphere adjoint exchange: item " + std::to_string(i) + " has dtype code " +
+                          std::to_string(dtypes[i]) + " (" + std::to_string(size) + " B) but elem_size " +
+                          std::to_string(cs_elem[size_t(i)]));
+        const int32_t kind = dtypes[i] <= GHX_DT_F64 ? 1 : 2;
+        if (cs_items[size_t(i)].is_vector && cs_items[size_t(i)].value_kind != kind)
+            throw invalid("cubed-sphere adjoint exchange: vector item " + std::to_string(i) + " has value_kind " +
+                          std::to_string(cs_items[size_t(i)].value_kind) + " but dtype code " +
+                          std::to_string(dtypes[i]) + " (1: GHX_DT_F32 / _F64, 2: GHX_DT_I32 / _I64)");
+    }
+    std::vector<int32_t> dt;
+    for (const ghx_pack_entry& e : entries[0]) dt.push_back(dtypes[e.field_slot]);
+    auto accum = std::make_unique<::ghx_saccum>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
+                                               int(entries[1].size()));
+    std::unique_ptr<splan> pack;
+    if (!cs_segs.empty()) pack = std::make_unique<splan>(cs_segs, cs_gf, cs_gb, cs_sbytes, 0);
+    cs_adj_accum = std::move(accum);
+    cs_adj_pack = std::move(pack);
+    cs_adj_ready = true;
 }
 
 int exchange_plan::execute_buffer(int dir, int b, void* const* fptr, int nf, void* const* bptr,

@@ -89,6 +89,20 @@ struct exchange_plan
     std::unique_ptr<splan> sadj_pack;
     std::unique_ptr<saccum_plan> sadj_accum;
     void make_sadjoint(const int32_t* dtypes, int32_t n);
+    // the adjoint of a cubed-sphere exchange (ghx_cs_exchange_adjoint_create). The
+    // reverse pack is the transpose of the unpack in its two parts: a pack plan over the ordinary
+    // receive segments (cs_segs: a copy of what sunpack was built from) and k_pack_x over xunpack's
+    // own records (no second tiler, no second upload). The accumulate plan is make_sadjoint's: the
+    // send side of a cubed-sphere exchange is ordinary boxes of the sender's field. ready: created.
+    std::vector<seg_s> cs_segs;
+    std::vector<int32_t> cs_gf, cs_gb;
+    uint64_t cs_sbytes = 0;
+    std::vector<ghx_cs_item> cs_items;  // per item, with its element size
+    std::vector<int32_t> cs_elem;
+    bool cs_adj_ready = false;
+    std::unique_ptr<splan> cs_adj_pack;  // null: no ordinary receive segment
+    std::unique_ptr<::ghx_saccum> cs_adj_accum;  // the handle type: ghx_cs_exchange_adjoint_plan lends it
+    void make_cs_adjoint(const int32_t* dtypes, int32_t n);
 
     void make_split();  // the per-buffer plans (ghx_exchange_split)
 

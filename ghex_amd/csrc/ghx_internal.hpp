@@ -463,6 +463,7 @@ int launch_unstructured(const kargs& a, int direction, void* stream, uint32_t gr
 int launch_self(const kargs& a, void* stream, uint32_t grid);
 int launch_put(const kargs& a, void* stream, uint32_t grid);
 int launch_unpack_x(const kargs& a, void* stream, uint32_t grid);  // tile_recs: seg_x records
+int launch_pack_x(const kargs& a, void* stream, uint32_t grid);    // the same records, field -> buffer
 int launch_self_cs(const kargs_cs& a, void* stream, uint32_t grid);
 int launch_put_cs(const kargs_pcs& a, void* stream, uint32_t grid);
 // tile_recs: seg_up records; field_ptr / buf_ptr: the source / target fields (as launch_put)

@@ -1054,6 +1054,63 @@ __global__ __launch_bounds__(kBlock) void k_unpack_x(kargs a)
     }
 }
 
+// The transpose of walk_x_tile<E, false, false> (the reverse pack of the cubed-sphere adjoint,
+// DESIGN.md §4.8): the same tile record, decode and offsets with the data direction reversed —
+// each lane loads its element of the receiving field, negates it where the transform does (the
+// sign matrix is diagonal: its transpose is itself) and stores it to its buffer cell. The tile is
+// still walked in field order, so a wave's loads cover whole field runs and its stores fall on a
+// few pieces of buffer rows. A sibling and not a flag of walk_x_tile: the three forward kernels
+// keep their code as it is.
+template<int E>
+__device__ __forceinline__ void pack_x_tile(const seg_x& s, const char* __restrict__ field,
+                                            char* __restrict__ cells, bool aligned)
+{
+    const uint32_t total = s.tdim[0] * s.tdim[1] * s.tdim[2] * s.tdim[3];
+    for (uint32_t i = threadIdx.x; i < total; i += kBlock)
+    {
+        uint32_t c[4];
+        if (!tile_decode(s, i, c)) continue;
+        auto v = load_elem<E>(affine_offset(field + s.field_off, s.stride, c), aligned);
+        if (s.neg_mask)  // uniform per tile: most tiles negate nothing
+        {
+            if (tile_negates(s, c)) v = negate_elem<E>(v, s.neg_kind);
+        }
+        store_elem<E>(cells + (size_t(tile_cell(s, c)) << E), v, aligned);
+    }
+}
+
+// Element-wide accesses when the field, the buffer and every field stride are element-aligned
+// (uniform per tile), as in walk_x.
+__device__ __forceinline__ void pack_x(const seg_x& s, const char* field, char* cells)
+{
+    const uint64_t em = (1u << s.elog2) - 1u;
+    const uint64_t strides = uint64_t(s.stride[0]) | uint64_t(s.stride[1]) | uint64_t(s.stride[2]) |
+                             uint64_t(s.stride[3]);
+    const bool aligned = (reinterpret_cast<uint64_t>(cells) & em) == 0 &&
+                         ((reinterpret_cast<uint64_t>(field) + uint64_t(s.field_off)) & em) == 0 &&
+                         (strides & em) == 0;
+    switch (s.elog2)
+    {
+        case 4: pack_x_tile<4>(s, field, cells, aligned); break;
+        case 3: pack_x_tile<3>(s, field, cells, aligned); break;
+        case 2: pack_x_tile<2>(s, field, cells, aligned); break;
+        case 1: pack_x_tile<1>(s, field, cells, aligned); break;
+        default: pack_x_tile<0>(s, field, cells, aligned); break;
+    }
+}
+
+// Transformed reverse pack: receiving field -> buffer cell, over k_unpack_x's own records.
+__global__ __launch_bounds__(kBlock) void k_pack_x(kargs a)
+{
+    const seg_x* __restrict__ recs = static_cast<const seg_x*>(a.tile_recs);
+    for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x)
+    {
+        const seg_x s = recs[t];
+        pack_x(s, reinterpret_cast<const char*>(a.field_ptr[s.field_slot]),
+               reinterpret_cast<char*>(a.buf_ptr[s.buf_slot]) + s.buf_off);
+    }
+}
+
 // Fused cubed-sphere self exchange: pack and rotating unpack of an exchange whose every message
 // stays on this device, in ONE launch. Blocks [0, n_pair_tiles) take a pair record as k_self's
 // record form does (spaces whose pack and unpack segments cover the same bytes with the same
@@ -1794,6 +1851,13 @@ int launch_unpack_x(const kargs& a, void* stream, uint32_t grid)
     if (a.n_tiles == 0) return GHX_OK;
     launch(k_unpack_x, min(grid, a.n_tiles), static_cast<hipStream_t>(stream), a);
     return launched("transformed unpack");
+}
+
+int launch_pack_x(const kargs& a, void* stream, uint32_t grid)
+{
+    if (a.n_tiles == 0) return GHX_OK;
+    launch(k_pack_x, min(grid, a.n_tiles), static_cast<hipStream_t>(stream), a);
+    return launched("transformed reverse pack");
 }
 
 int launch_self_cs(const kargs_cs& a, void* stream, uint32_t grid)

@@ -765,6 +765,14 @@ int xplan::execute(void* const* fptr, int nf, void* const* bptr, int nb, void* s
                           });
 }
 
+int xplan::execute_pack(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
+{
+    return execute_groups(*this, nullptr, fptr, nf, bptr, nb,
+                          [&](const kargs& a, const launch_group<seg_x>&) {
+                              return launch_pack_x(a, stream, grid_for_tiles(a.n_tiles));
+                          });
+}
+
 // ---------------------------------------------------------------------------------------------
 // fused cubed-sphere self exchange and cubed-sphere put
 // ---------------------------------------------------------------------------------------------

@@ -125,6 +125,8 @@ struct xplan
     std::vector<launch_group<seg_x>> groups;  // host_segs: the tile records, dev.recs on the device
     explicit xplan(std::vector<xseg> boxes);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
+    // the transpose (k_pack_x): the same records and tables, receiving field -> buffer
+    int execute_pack(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
 };
 // where a tile record lies in its box: the tile's origin per BUFFER axis of the xseg, and the
 // buffer axis each of the record's (stride-sorted) axes is
@@ -347,6 +349,10 @@ int run_structured(const ghx_field_desc& f, const ghx_box* boxes, int n, int dir
 int run_cs_unpack(const ghx_field_desc& f, const ghx_cs_item& cs, const ghx_box* local,
                   const ghx_box* global, const int32_t* tiles, int n, void* field, void* buffer,
                   void* stream);
+// the transpose of run_cs_unpack (ghx_cs_pack_rotated): the same cached plan, field -> buffer
+int run_cs_pack_rotated(const ghx_field_desc& f, const ghx_cs_item& cs, const ghx_box* local,
+                        const ghx_box* global, const int32_t* tiles, int n, const void* field,
+                        void* buffer, void* stream);
 int run_unstructured(const ghx_udata_desc& d, const void* lids, int32_t lid_bytes, int64_t n,
                      int dir, void* values, void* buffer, void* stream);
 }  // namespace ghx

@@ -20,12 +20,15 @@ from ..pattern import PatternContainer
 from .regular import _layout_order
 
 
-def make_communication_object(context, fuse_rotated: bool = False,
+def make_communication_object(context, fuse_rotated: bool = False, adjoint_rotated: bool = False,
                               **options) -> CommunicationObject:
     """The plain communication object. fuse_rotated=True (opt-in): an exchange whose every
     message stays on this rank (a whole cube on one rank) runs as ONE launch that packs and
-    rotates (ghx_cs_exchange_self); any other exchange takes the usual three launches."""
-    return CommunicationObject(context, fuse_rotated=fuse_rotated, **options)
+    rotates (ghx_cs_exchange_self); any other exchange takes the usual three launches.
+    adjoint_rotated=True (opt-in): adjoint_exchange and its siblings take cubed-sphere fields
+    (ghx_cs_exchange_adjoint_*: a reverse pack that rotates and negates, then the accumulate)."""
+    return CommunicationObject(context, fuse_rotated=fuse_rotated, adjoint_rotated=adjoint_rotated,
+                               **options)
 
 
 def make_bulk_communication_object(context, epochs: str = "device", timeout: float = 30.0,
@@ -224,6 +227,18 @@ class FieldDescriptor:
     def edge_size(self) -> int:
         return self.domain.cube.edge_size
 
+    def dtype_code(self) -> int:
+        """The element type code of the adjoint exchange (GHX_DT_*), as
+        regular.FieldDescriptor.dtype_code. TypeError for a dtype it does not sum."""
+        import torch
+        codes = {torch.float32: _ghx.DT_F32, torch.float64: _ghx.DT_F64,
+                 torch.int32: _ghx.DT_I32, torch.int64: _ghx.DT_I64}
+        code = codes.get(self.tensor.dtype)
+        if code is None:
+            raise TypeError(f"adjoint exchange: dtype {self.tensor.dtype} is not supported "
+                            "(float32, float64, int32, int64)")
+        return code
+
     def data_ptr(self) -> int:
         return self.tensor.data_ptr()
 
@@ -256,6 +271,18 @@ class FieldDescriptor:
         bp = buffer.data_ptr() if hasattr(buffer, "data_ptr") else int(buffer)
         tiles = _ghx.i32_array([int(sp[4]) for sp in spaces])
         _ghx.call("ghx_cs_unpack", ctypes.byref(self.desc), ctypes.byref(self.cs_item),
+                  self.data_ptr(), bp, self._boxes(spaces, 0, 1), self._boxes(spaces, 2, 3),
+                  tiles, len(spaces), s)
+
+    def pack_rotated(self, buffer, spaces, stream=None):
+        """The transpose of unpack (ghx_cs_pack_rotated): the field's cells of the spaces' local
+        boxes go to the buffer positions unpack reads them from, negated where unpack negates.
+        The field is read, the buffer written; spaces as unpack takes them."""
+        import torch
+        s = (stream or torch.cuda.current_stream()).cuda_stream
+        bp = buffer.data_ptr() if hasattr(buffer, "data_ptr") else int(buffer)
+        tiles = _ghx.i32_array([int(sp[4]) for sp in spaces])
+        _ghx.call("ghx_cs_pack_rotated", ctypes.byref(self.desc), ctypes.byref(self.cs_item),
                   self.data_ptr(), bp, self._boxes(spaces, 0, 1), self._boxes(spaces, 2, 3),
                   tiles, len(spaces), s)
 

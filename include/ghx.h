@@ -616,6 +616,16 @@ int ghx_cs_exchange_self(const ghx_exchange* ex, void* const* field_ptrs, int32_
 int ghx_cs_unpack(const ghx_field_desc* field, const ghx_cs_item* cs, void* field_data,
                   const void* buffer, const ghx_box* local, const ghx_box* global,
                   const int32_t* tiles, int32_t n_boxes, ghx_stream stream);
+/* The transpose of ghx_cs_unpack for ONE field, with the same arguments and the same cached plan:
+ * the field is READ and the buffer is WRITTEN. Every cell of every local box goes to the buffer
+ * position ghx_cs_unpack reads it from, negated where ghx_cs_unpack negates (the sign matrix is
+ * diagonal: its transpose is itself), so ghx_cs_unpack(ghx_cs_pack_rotated(R)) restores the boxes
+ * of R bit for bit. Ordinary spaces run a pack launch, transformed ones k_pack_x over the
+ * records k_unpack_x reads. Every element size ghx_cs_unpack takes. The reference has no
+ * counterpart (its cubed-sphere descriptor packs unrotated, field_descriptor.hpp:110-140). */
+int ghx_cs_pack_rotated(const ghx_field_desc* field, const ghx_cs_item* cs, const void* field_data,
+                        void* buffer, const ghx_box* local, const ghx_box* global,
+                        const int32_t* tiles, int32_t n_boxes, ghx_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Zero-copy put between node-local GPUs. Replaces the reference's RMA path:
@@ -1051,6 +1061,46 @@ int ghx_sexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, 
 int ghx_sexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
                                      int32_t n_fields, void* const* send_buffers, int32_t n_send,
                                      int32_t zero_halos, ghx_stream stream);
+
+/* The adjoint of a cubed-sphere exchange (ghx_cs_exchange_create), the third twin. The forward
+ * unpack sets R[x, y, z, k] = s_k * B[T(x, y), z, k] (B the dense box in the neighbour tile's
+ * coordinates, s_k = -1 for the vector components the edge's transform negates); the transpose is
+ *   1. the reverse pack  B[T(x, y), z, k] = s_k * R[x, y, z, k]  into the RECEIVE buffers: a pack
+ *      launch over the exchange's ordinary receive segments, then k_pack_x over the transformed
+ *      unpack's own tile records (no second table);
+ *   2. after the transport with the roles swapped (a self message's receive buffer is its send
+ *      buffer), S[send cell] += B[cell] for every send entry, box and cell in ascending (send
+ *      entry, box): ghx_saccum_create's plan over the exchange's send entries (the send side of a
+ *      cubed-sphere exchange is ordinary boxes of the sender's field), bitwise reproducible, no
+ *      atomics; with zero_halos zero bytes are then stored into every receive box. Halo cells no
+ *      receive box holds (the cube-corner squares) keep their values.
+ * dtypes[i] is the GHX_DT_* code of item i. create: GHX_ERR_INVALID, with the reason, for an
+ * exchange that is not a cubed-sphere exchange, while a direction has parity set, when n_items is
+ * not the exchange's or a code is unknown, when a code's size differs from the item's elem_size,
+ * when a vector item's value_kind disagrees with its code (1: F32 / F64, 2: I32 / I64), and for
+ * ghx_saccum_create's reasons (more than 64 field or buffer slots among them: a whole 24-domain
+ * cube on one rank has 168 buffers; split it over ranks). info works on any exchange and without a
+ * device: the sum sub-boxes and source records of the accumulate plan, and the records (spaces)
+ * and tiles k_pack_x runs (ghx_cs_plan_info's). plan lends the accumulate plan (owned by the
+ * exchange) to ghx_saccum_info / _box / _source. pack has ghx_exchange_unpack's argument contract
+ * (it writes the RECEIVE buffers), accumulate ghx_exchange_pack's (it reads the SEND buffers);
+ * both fail with GHX_ERR_INVALID before create and while a direction has parity set, allocate
+ * nothing and can be captured in a graph. ghx_sexchange_adjoint_create and
+ * ghx_uexchange_adjoint_create refuse a cubed-sphere exchange as before. */
+int ghx_cs_exchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items);
+int ghx_cs_exchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_boxes,
+                                 int64_t* n_sources, int32_t* n_pack_x_records,
+                                 int32_t* n_pack_x_tiles);
+int ghx_cs_exchange_adjoint_plan(const ghx_exchange* ex, const ghx_saccum** out);
+/* The ordinary part of the reverse pack next to the ordinary part of the unpack it transposes:
+ * their segment counts (equal once created; 0 before create / on any other exchange). */
+int ghx_cs_exchange_adjoint_segments(const ghx_exchange* ex, int32_t* n_pack_segments,
+                                     int32_t* n_unpack_segments);
+int ghx_cs_exchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                 void* const* recv_buffers, int32_t n_recv, ghx_stream stream);
+int ghx_cs_exchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
+                                       int32_t n_fields, void* const* send_buffers, int32_t n_send,
+                                       int32_t zero_halos, ghx_stream stream);
 
 /* Device-side access epochs of the zero-copy exchanges (bulk puts, direct pack): the reference's
  * access guards (include/ghex/rma/access_guard.hpp:35-140; per range: start/end_target_epoch on
