@@ -176,6 +176,13 @@ _SIGS = {
     "ghx_saccum_box": (c_i32, [c_vp, c_i64, P(SAccumBoxInfo)]),
     "ghx_saccum_source": (c_i32, [c_vp, c_i64, P(c_i32), P(c_i32), P(c_i32), P(c_u64)]),
     "ghx_saccum_destroy": (c_i32, [c_vp]),
+    "ghx_saccum_get_create": (c_i32, [P(PackEntry), P(c_i32), P(P(PackEntry)), c_i32, P(PackEntry), c_i32, P(c_vp)]),
+    "ghx_saccum_get_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
+    "ghx_saccum_source_kind": (c_i32, [c_vp, c_i64, P(c_i32), P(c_i32), P(c_u64)]),
+    "ghx_sexchange_adjoint_self_create": (c_i32, [c_vp, P(c_i32), c_i32]),
+    "ghx_sexchange_adjoint_self_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i64)]),
+    "ghx_sexchange_adjoint_self_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_sexchange_adjoint_self_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_sexchange_adjoint_create": (c_i32, [c_vp, P(c_i32), c_i32]),
     "ghx_sexchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64)]),
     "ghx_sexchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),

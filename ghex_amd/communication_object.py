@@ -253,7 +253,8 @@ class CommunicationObject:
                  rccl_self: bool = False, max_streams: int = 4, copy_engine: str = "probe",
                  direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False,
                  fuse_lists: bool = False, fuse_lists_mixed: bool = False,
-                 adjoint_boxes: bool = False, adjoint_rotated: bool = False):
+                 adjoint_boxes: bool = False, adjoint_rotated: bool = False,
+                 fuse_adjoint: bool = False):
         if staging not in (None, "host"):
             raise ValueError("staging must be None (device buffers) or 'host'")
         if direct and (staging is not None or pipelined or rccl_self):
@@ -292,6 +293,14 @@ class CommunicationObject:
         # unpack does (ghx_cs_exchange_adjoint_*, k_pack_x), the accumulate is k_accum_s. Opt-in;
         # without it a cubed-sphere field is refused, as before
         self.adjoint_rotated = bool(adjoint_rotated)
+        # the adjoint of regular structured fields with the self messages fused: their halo cells
+        # are added straight into their owner cells in the accumulate launch
+        # (ghx_sexchange_adjoint_self_*, k_accum_get_s); the buffers of self messages are not
+        # touched. Opt-in, with adjoint_boxes; a plan without a self message takes the usual path
+        if fuse_adjoint and not adjoint_boxes:
+            raise ValueError("fuse_adjoint fuses the adjoint of regular structured fields: it needs "
+                             "adjoint_boxes=True")
+        self.fuse_adjoint = bool(fuse_adjoint)
         self.staging = staging
         self.pipelined = pipelined
         # tests: route the self messages through RCCL too (a 1-rank communicator), so the
@@ -603,12 +612,17 @@ class CommunicationObject:
                 raise ValueError("the adjoint exchange takes unstructured fields only (structured "
                                  "and cubed-sphere send boxes overlap)")
         # boxes: ghx_sexchange_adjoint_* (k_accum_s), lists: ghx_uexchange_adjoint_* (k_accum_u)
+        if boxes and self.fuse_adjoint and self.fuse_self:
+            me = self.context.rank()
+            if any(x["rank"] == me for x in self.plan(bis).recv):
+                # all self or mixed: the self messages come from the halos (k_accum_get_s)
+                return self._with_adjoint(bis, "ghx_sexchange_adjoint_self_")
         return self._with_adjoint(bis, "ghx_sexchange_adjoint_" if boxes else "ghx_uexchange_adjoint_")
 
     def _with_adjoint(self, bis, prefix):
         codes = [bi.field.dtype_code() for bi in bis]  # TypeError for any other dtype
         plan = self.plan(bis)
-        if getattr(plan, "_adjoint_codes", None) != codes:
+        if getattr(plan, "_adjoint_codes", None) != codes or plan._adjoint_prefix != prefix:
             _ghx.call(prefix + "create", plan.h, _ghx.i32_array(codes), len(codes))
             plan._adjoint_codes = codes
             plan._adjoint_prefix = prefix
@@ -622,7 +636,11 @@ class CommunicationObject:
         fixed order (bitwise reproducible, no atomics); with zero_halos the halo cells are then
         set to zero (the true transpose), without it they keep their values (assembly). The plain
         path: reverse pack into the receive buffers, the forward transport with the roles
-        swapped, accumulate from the send buffers."""
+        swapped, accumulate from the send buffers. On an object made with fuse_adjoint=True (and
+        fuse_self), regular structured fields whose plan has a self message take the fused form:
+        the reverse pack gathers the peer messages only, the transport carries them as before,
+        and the accumulate reads the self messages from the halo cells themselves. The send and
+        receive buffers of self messages are then not touched: they keep whatever they held."""
         import torch
         bis = self._as_list(buffer_infos)
         stream = torch.cuda.current_stream(bis[0].field.device.index) if bis else None

@@ -1424,6 +1424,42 @@ int ghx_saccum_source(const ghx_saccum* p, int64_t j, int32_t* entry, int32_t* b
     });
 }
 
+int ghx_saccum_get_create(const ghx_pack_entry* contrib, const int32_t* dtypes, const ghx_pack_entry* const* source,
+                          int32_t n, const ghx_pack_entry* zero, int32_t n_zero, ghx_saccum** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        *out = nullptr;
+        if (n < 0 || n_zero < 0 || (n && (!contrib || !dtypes)) || (n_zero && !zero)) throw invalid("bad entry arrays");
+        check_ptr(source, "source");
+        *out = new ghx_saccum(contrib, dtypes, n, zero, n_zero, source);
+        return GHX_OK;
+    });
+}
+
+int ghx_saccum_get_execute(const ghx_saccum* p, void* const* field_ptrs, int32_t n_fields,
+                           void* const* buffer_ptrs, int32_t n_buffers, int32_t zero_halos,
+                           ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        return p->execute_get(field_ptrs, n_fields, buffer_ptrs, n_buffers, zero_halos != 0, stream);
+    });
+}
+
+int ghx_saccum_source_kind(const ghx_saccum* p, int64_t j, int32_t* kind, int32_t* slot, uint64_t* offset_of_origin)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (j < 0 || uint64_t(j) >= p->srcs.size()) throw invalid("source index out of range");
+        const sacc_src& s = p->srcs[size_t(j)];
+        if (kind) *kind = (s.flags & kSaccFieldSrc) ? 1 : 0;
+        if (slot) *slot = p->get ? p->tab_slot[s.buf_slot] : int32_t(s.buf_slot);
+        if (offset_of_origin) *offset_of_origin = s.buf_off;
+        return GHX_OK;
+    });
+}
+
 int ghx_saccum_destroy(ghx_saccum* p)
 {
     return guarded([&] {
@@ -1485,6 +1521,65 @@ int ghx_sexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_
         check_sadjoint(ex);
         if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
         return ex->sadj_accum->execute(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
+    });
+}
+
+int ghx_sexchange_adjoint_self_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        ex->make_sadjoint_self(dtypes, n_items);
+        return GHX_OK;
+    });
+}
+
+int ghx_sexchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64_t* n_boxes, int64_t* n_sources,
+                                    int64_t* n_field_sources)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(form, "form");
+        const saccum_plan* p = ex->sself_accum.get();
+        *form = p ? ex->sself_form : 0;
+        if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
+        if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
+        if (n_field_sources) *n_field_sources = p ? int64_t(p->n_field_sources) : 0;
+        return GHX_OK;
+    });
+}
+
+namespace
+{
+void check_sadjoint_self(const ghx_exchange* ex)
+{
+    check_ptr(ex, "exchange");
+    if (!ex->sself_accum)
+        throw invalid("fused adjoint exchange: no plans (ghx_sexchange_adjoint_self_create)");
+    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+}
+}  // namespace
+
+int ghx_sexchange_adjoint_self_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                    void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
+{
+    return guarded([&] {
+        check_sadjoint_self(ex);
+        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
+        if (!ex->sself_pack) return int(GHX_OK);  // every message is a self message: nothing to gather
+        return ex->sself_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+    });
+}
+
+int ghx_sexchange_adjoint_self_accumulate(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                          void* const* send_buffers, int32_t n_send, int32_t zero_halos,
+                                          ghx_stream stream)
+{
+    return guarded([&] {
+        check_sadjoint_self(ex);
+        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
+        return ex->sself_accum->execute_get(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
     });
 }
 

@@ -203,7 +203,46 @@ __device__ __forceinline__ V load_src(const kargs_sa& a, const GHX_CONST sacc_sr
     return *(const GHX_GLOBAL V*)(b + off);
 }
 
-template<typename T, int W>
+// k_accum_get_s: where that vector lies, and the record's flags word. A field source (flags bit 0)
+// is a receiving field's halo cells, read in place of a buffer
+template<typename V>
+__device__ __forceinline__ GHX_GLOBAL V* src_addr(const kargs_sa& a, const GHX_CONST sacc_src* srcs, uint32_t j,
+                                                  const uint32_t (&c)[4], uint32_t col, bool deep, uint32_t& flags)
+{
+    const GHX_CONST u32x4* p = (const GHX_CONST u32x4*)(srcs + j);
+    const u32x4 r0 = p[0], r1 = p[1], r2 = p[2];
+    char* b = reinterpret_cast<char*>(a.buf_ptr[r2.z]) + u64_of(r0.x, r0.y);
+    uint64_t off = uint64_t(c[0]) * u64_of(r0.z, r0.w) + uint64_t(c[1]) * u64_of(r1.x, r1.y) + col;
+    if (deep) off += uint64_t(c[2]) * u64_of(r1.z, r1.w) + uint64_t(c[3]) * u64_of(r2.x, r2.y);
+    flags = r2.w;
+    return (GHX_GLOBAL V*)(b + off);
+}
+
+// the loads of N sources from record j on, issued together; then, in a launch with zero_halos, zero
+// bytes over those that are field sources (a wave-uniform branch per source: the flags come from the
+// scalar path), each by the lane that loaded it; then the adds, in list order
+template<typename V, int N>
+__device__ __forceinline__ V get_batch(const kargs_sa& a, const GHX_CONST sacc_src* srcs, uint32_t j,
+                                       const uint32_t (&c)[4], uint32_t col, bool deep, V acc)
+{
+    GHX_GLOBAL V* p[N];
+    uint32_t fl[N];
+    V v[N];
+#pragma unroll
+    for (uint32_t k = 0; k < uint32_t(N); ++k)
+    {
+        p[k] = src_addr<V>(a, srcs, j + k, c, col, deep, fl[k]);
+        v[k] = *p[k];
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < uint32_t(N); ++k)
+        if (a.zero_src & fl[k]) *p[k] = V(0);
+#pragma unroll
+    for (uint32_t k = 0; k < uint32_t(N); ++k) acc = acc + v[k];
+    return acc;
+}
+
+template<typename T, int W, bool Get = false>
 __device__ __forceinline__ void accum_tile_s(const kargs_sa& a, const sacc_tile& s, const GHX_CONST sacc_src* srcs)
 {
     typedef typename vec_of<T, W / int(sizeof(T))>::type V;
@@ -220,6 +259,16 @@ __device__ __forceinline__ void accum_tile_s(const kargs_sa& a, const sacc_tile&
         GHX_GLOBAL V* cell = (GHX_GLOBAL V*)(field + foff);
         V acc = *cell;
         uint32_t j = s.first_src, left = s.n_src;  // uniform
+        if constexpr (Get)
+        {
+            for (; left >= uint32_t(kAccBatch); j += kAccBatch, left -= kAccBatch)
+                acc = get_batch<V, kAccBatch>(a, srcs, j, c, col, deep, acc);
+            if (left == 3) acc = get_batch<V, 3>(a, srcs, j, c, col, deep, acc);
+            else if (left == 2) acc = get_batch<V, 2>(a, srcs, j, c, col, deep, acc);
+            else if (left == 1) acc = get_batch<V, 1>(a, srcs, j, c, col, deep, acc);
+            *cell = acc;
+            continue;
+        }
         while (left >= uint32_t(kAccBatch))
         {
             V v[kAccBatch];
@@ -267,16 +316,17 @@ __device__ __forceinline__ void zero_tile_s(const kargs_sa& a, const sacc_tile& 
     }
 }
 
-template<typename T>
+template<typename T, bool Get = false>
 __device__ __forceinline__ void accum_tile_sw(const kargs_sa& a, const sacc_tile& s, const GHX_CONST sacc_src* srcs, int w)
 {
-    if (w == 4) accum_tile_s<T, 16>(a, s, srcs);
-    else if constexpr (sizeof(T) == 8) accum_tile_s<T, 8>(a, s, srcs);
-    else if (w == 3) accum_tile_s<T, 8>(a, s, srcs);
-    else accum_tile_s<T, 4>(a, s, srcs);
+    if (w == 4) accum_tile_s<T, 16, Get>(a, s, srcs);
+    else if constexpr (sizeof(T) == 8) accum_tile_s<T, 8, Get>(a, s, srcs);
+    else if (w == 3) accum_tile_s<T, 8, Get>(a, s, srcs);
+    else accum_tile_s<T, 4, Get>(a, s, srcs);
 }
 
-__global__ __launch_bounds__(kBlock) void k_accum_s(kargs_sa a)
+template<bool Get>
+__device__ __forceinline__ void accum_tiles_s(const kargs_sa& a)
 {
     const GHX_CONST sacc_tile* tiles = (const GHX_CONST sacc_tile*)reinterpret_cast<uintptr_t>(a.tiles);
     const GHX_CONST sacc_src* srcs = (const GHX_CONST sacc_src*)reinterpret_cast<uintptr_t>(a.srcs);
@@ -290,15 +340,23 @@ __global__ __launch_bounds__(kBlock) void k_accum_s(kargs_sa a)
             else if (w == 3) zero_tile_s<8>(a, s);
             else zero_tile_s<4>(a, s);
         }
-        else if (s.dtype == GHX_DT_F32) accum_tile_sw<float>(a, s, srcs, w);
-        else if (s.dtype == GHX_DT_F64) accum_tile_sw<double>(a, s, srcs, w);
-        else if (s.dtype == GHX_DT_I64) accum_tile_sw<uint64_t>(a, s, srcs, w);
-        else accum_tile_sw<uint32_t>(a, s, srcs, w);
+        else if (s.dtype == GHX_DT_F32) accum_tile_sw<float, Get>(a, s, srcs, w);
+        else if (s.dtype == GHX_DT_F64) accum_tile_sw<double, Get>(a, s, srcs, w);
+        else if (s.dtype == GHX_DT_I64) accum_tile_sw<uint64_t, Get>(a, s, srcs, w);
+        else accum_tile_sw<uint32_t, Get>(a, s, srcs, w);
     }
 }
-}  // namespace
 
-int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid)
+__global__ __launch_bounds__(kBlock) void k_accum_s(kargs_sa a) { accum_tiles_s<false>(a); }
+
+// k_accum_get_s: k_accum_s's walk with a source taken from the buffers or, a field source, from the
+// halo cells of a receiving field of the same launch (ghx_saccum_get_create). The planner has
+// verified that one (cell, source) pair reads a halo cell and that nothing else touches it, so the
+// lane that loaded a halo vector may store zero bytes over it (zero_halos) with no other ordering.
+__global__ __launch_bounds__(kBlock) void k_accum_get_s(kargs_sa a) { accum_tiles_s<true>(a); }
+
+template<typename K>
+int launch_sa(K kernel, const char* what, const kargs_sa& a, void* stream, uint32_t grid)
 {
     if (a.n_tiles == 0) return GHX_OK;
     grid = grid < a.n_tiles ? grid : a.n_tiles;
@@ -306,21 +364,32 @@ int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (t_timing && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
     {
-        hipExtLaunchKernelGGL(k_accum_s, dim3(grid), dim3(kBlock), 0, s, e0, e1, 0, a);
+        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, e0, e1, 0, a);
         t_timing->emplace_back(e0, e1);
     }
     else
     {
         if (e0) (void)hipEventDestroy(e0);
-        hipLaunchKernelGGL(k_accum_s, dim3(grid), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, a);
     }
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
     {
-        set_error(std::string("structured adjoint accumulate kernel launch failed: ") + hipGetErrorString(err));
+        set_error(std::string(what) + " kernel launch failed: " + hipGetErrorString(err));
         return GHX_ERR_HIP;
     }
     return GHX_OK;
+}
+}  // namespace
+
+int launch_accum_get_s(const kargs_sa& a, void* stream, uint32_t grid)
+{
+    return launch_sa(k_accum_get_s, "structured adjoint get-accumulate", a, stream, grid);
+}
+
+int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid)
+{
+    return launch_sa(k_accum_s, "structured adjoint accumulate", a, stream, grid);
 }
 
 int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid)

@@ -192,11 +192,11 @@ void plan_direction(const ghx_exchange_item* items, int n_items, bool receive,
 // and the unpack launch covers the peer messages only. Companion segment k of the pack plan is
 // the unpack segment of the same buffer bytes for a self message (same tiling, checked), or
 // zero for a peer message. `rent` = the receive-side pack entries of every recv buffer.
-void build_mixed(exchange_plan& ex, int32_t me, const std::vector<ghx_pack_entry>& rent)
+// per recv buffer of rank `me` the send buffer of the same pair of domains, size and rank: a self
+// message, whose recv buffer IS its send buffer; -1 for a peer's
+std::vector<int> self_pairs(const exchange_plan& ex, int32_t me)
 {
-    if (!ex.spack || !ex.sunpack || ex.upack || ex.uunpack || me < 0 || ex.self_fusable()) return;
     std::vector<int> send_of_recv(ex.recv.size(), -1);
-    bool any_self = false;
     for (size_t j = 0; j < ex.recv.size(); ++j)
     {
         const xbuffer& r = ex.recv[j];
@@ -208,11 +208,18 @@ void build_mixed(exchange_plan& ex, int32_t me, const std::vector<ghx_pack_entry
                 s.size == r.size)
             {
                 send_of_recv[j] = int(i);
-                any_self = true;
                 break;
             }
         }
     }
+    return send_of_recv;
+}
+
+void build_mixed(exchange_plan& ex, int32_t me, const std::vector<ghx_pack_entry>& rent)
+{
+    if (!ex.spack || !ex.sunpack || ex.upack || ex.uunpack || me < 0 || ex.self_fusable()) return;
+    const std::vector<int> send_of_recv = self_pairs(ex, me);
+    const bool any_self = std::any_of(send_of_recv.begin(), send_of_recv.end(), [](int i) { return i >= 0; });
     if (!any_self) return;
     std::vector<ghx_pack_entry> self_e, peer_e;
     for (const ghx_pack_entry& e : rent)
@@ -752,6 +759,10 @@ std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, cons
         upload_pair_records(ex->self_recs, p.first().host_segs, q.first().host_segs,
                             p.first().host_tiles);
     }
+    // the self messages (make_sadjoint_self): buffer k of both sides when every message is one
+    ex->send_of_recv = self_pairs(*ex, items[0].pattern->my_rank);
+    if (ex->self_ok)
+        for (size_t j = 0; j < ex->recv.size(); ++j) ex->send_of_recv[j] = int(j);
     if (ex->cs_rotated == 0) build_mixed(*ex, items[0].pattern->my_rank, rent);
     if (cs) build_cs_self(*ex, cs, items[0].pattern->my_rank, rhalos);
     else ex->cs_self_reason = "not fusable: not a cubed-sphere exchange";
@@ -834,6 +845,65 @@ void exchange_plan::make_sadjoint(const int32_t* dtypes, int32_t n)
     auto pack = std::make_unique<splan>(entries[1].data(), int(entries[1].size()), 0);
     sadj_accum = std::move(accum);
     sadj_pack = std::move(pack);
+}
+
+void exchange_plan::make_sadjoint_self(const int32_t* dtypes, int32_t n)
+{
+    if (cubed_sphere)
+        throw invalid("adjoint exchange: the exchange holds a cubed-sphere item (its adjoint would rotate and "
+                      "flip signs; only regular structured items take ghx_sexchange_adjoint_self_create)");
+    if (!only_structured)
+        throw invalid("adjoint exchange: the exchange holds an unstructured item (an exchange mixing structured "
+                      "and unstructured items has no adjoint; index-list items take ghx_uexchange_adjoint_create)");
+    if (dir_parity[0].word || dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+    if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
+    for (int32_t i = 0; i < n; ++i)
+        if (dtypes[i] < GHX_DT_F32 || dtypes[i] > GHX_DT_I64)
+            throw invalid("unknown dtype code " + std::to_string(dtypes[i]) + " (GHX_DT_F32, _F64, _I32, _I64)");
+    // the receive entry at the same message bytes sources a self message's send entry
+    std::vector<int> recv_of_send(send.size(), -1);
+    for (size_t j = 0; j < send_of_recv.size(); ++j)
+        if (send_of_recv[j] >= 0) recv_of_send[size_t(send_of_recv[j])] = int(j);
+    std::vector<int32_t> dt;
+    std::vector<const ghx_pack_entry*> source;
+    std::vector<char> sourced(entries[1].size(), 0);
+    size_t n_self = 0;
+    for (const ghx_pack_entry& e : entries[0])
+    {
+        dt.push_back(dtypes[e.field_slot]);
+        source.push_back(nullptr);
+        const int j = recv_of_send[size_t(e.buffer_slot)];
+        if (j < 0) continue;
+        for (size_t k = 0; k < entries[1].size() && !source.back(); ++k)
+            if (entries[1][k].buffer_slot == j && entries[1][k].buffer_offset == e.buffer_offset)
+            {
+                source.back() = &entries[1][k];
+                sourced[k] = 1;
+            }
+        if (!source.back())
+            throw invalid("fused adjoint: a send entry of a self message has no receive entry at the same "
+                          "message bytes");
+        ++n_self;
+    }
+    if (n_self == 0) throw invalid("fused adjoint: the exchange has no self message (ghx_sexchange_adjoint_create)");
+    std::vector<ghx_pack_entry> peer;
+    for (size_t k = 0; k < entries[1].size(); ++k)
+    {
+        if (sourced[k]) continue;
+        if (send_of_recv[size_t(entries[1][k].buffer_slot)] >= 0)
+            throw invalid("fused adjoint: a receive entry of a self message has no send entry at the same "
+                          "message bytes");
+        peer.push_back(entries[1][k]);
+    }
+    auto accum = std::make_unique<saccum_plan>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
+                                               int(entries[1].size()), source.data());
+    std::unique_ptr<splan> pack;
+    if (!peer.empty()) pack = std::make_unique<splan>(peer.data(), int(peer.size()), 0);
+    sself_form = n_self == entries[0].size() && peer.empty() ? 1 : 2;
+    sself_accum = std::move(accum);
+    sself_pack = std::move(pack);
 }
 
 void exchange_plan::make_cs_adjoint(const int32_t* dtypes, int32_t n)

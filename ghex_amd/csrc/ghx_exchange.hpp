@@ -89,6 +89,16 @@ struct exchange_plan
     std::unique_ptr<splan> sadj_pack;
     std::unique_ptr<saccum_plan> sadj_accum;
     void make_sadjoint(const int32_t* dtypes, int32_t n);
+    // the same adjoint with the self messages fused (ghx_sexchange_adjoint_self_create): the get
+    // plan (k_accum_get_s) reads a self message from the receiving field's halo cells, and the
+    // reverse pack covers the peer receive entries alone (null: every message is a self message).
+    // send_of_recv: per recv buffer the send buffer of the same self message or -1 (self_pairs,
+    // the match of build_mixed), set by make_exchange. form: 0 none, 1 all self, 2 mixed.
+    std::vector<int> send_of_recv;
+    int32_t sself_form = 0;
+    std::unique_ptr<splan> sself_pack;
+    std::unique_ptr<saccum_plan> sself_accum;
+    void make_sadjoint_self(const int32_t* dtypes, int32_t n);
     // the adjoint of a cubed-sphere exchange (ghx_cs_exchange_adjoint_create). The
     // reverse pack is the transpose of the unpack in its two parts: a pack plan over the ordinary
     // receive segments (cs_segs: a copy of what sunpack was built from) and k_pack_x over xunpack's

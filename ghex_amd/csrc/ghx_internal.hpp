@@ -387,10 +387,12 @@ struct alignas(16) sacc_src
 {
     uint64_t buf_off;     // byte offset in the buffer of the sub-box's origin
     uint64_t stride[4];   // buffer byte stride of outer dim k of the sub-box in this box
-    uint32_t buf_slot;
-    uint32_t pad;
+    uint32_t buf_slot;    // index in the launch's source pointer table (kargs_sa::buf_ptr)
+    uint32_t flags;       // bit 0: a field source (k_accum_get_s: a receiving field's halo cells,
+                          // zeroed after the load when the launch has zero_halos); else 0
 };
 static_assert(sizeof(sacc_src) == 48, "sacc_src layout");
+constexpr uint32_t kSaccFieldSrc = 1u;
 // Tile record, one per workgroup tile: the sub-box with the tile's part of it — n_rows rows from
 // first_row on, of each the `len` bytes from byte col0 on (col0 > 0 only where one row is longer
 // than a tile: then n_rows = 1 and col0 a multiple of 16). A lane takes one vector of the tile's
@@ -423,9 +425,11 @@ struct kargs_sa
     const sacc_tile* tiles;
     const sacc_src* srcs;
     uint32_t n_tiles;
-    uint32_t pad;
-    uint64_t buf_mis8, buf_mis16;  // bit b: buffer pointer b is not 8- / 16-byte aligned
+    uint32_t zero_src;             // k_accum_get_s: store zero bytes over a field source once loaded
+    uint64_t buf_mis8, buf_mis16;  // bit b: source pointer b is not 8- / 16-byte aligned
     uint64_t field_ptr[GHX_MAX_SLOTS];
+    // the source pointer table: the buffers; in a get plan the buffers that are read, then the
+    // source fields (saccum_plan::tab_slot)
     uint64_t buf_ptr[GHX_MAX_SLOTS];
 };
 
@@ -476,6 +480,7 @@ int launch_pack_self_u(const kargs_um& a, void* stream, uint32_t grid, bool runs
 // ghx_accum.hip: the adjoint accumulate over the first a.n_tiles tile records
 int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid);
 int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid);
+int launch_accum_get_s(const kargs_sa& a, void* stream, uint32_t grid);  // k_accum_get_s
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

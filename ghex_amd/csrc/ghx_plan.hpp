@@ -337,9 +337,18 @@ struct saccum_plan
         tables& operator=(const tables&) = delete;
         ~tables();
     } dev;
+    // A get plan (ghx_saccum_get_create, k_accum_get_s): `source` names per contribution entry the
+    // halo side of the same message (null: the entry reads its buffer). Source records then index
+    // the table tab_slot: first the buffer slots that are read, ascending, then the source field
+    // slots, ascending (tab_field: from where on). A zero entry that is a contribution's source
+    // (same field slot, same boxes) gets no zero tile: the accumulate zeroes it as it reads.
+    bool get = false;
+    std::vector<int32_t> tab_slot;
+    uint32_t tab_field = 0, n_field_sources = 0;
     saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, int n, const ghx_pack_entry* zero,
-                int n_zero);
+                int n_zero, const ghx_pack_entry* const* source = nullptr);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
+    int execute_get(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
 };
 
 // The per-call entry points' plans, cached by content (ghx_cache.cpp): the plan of the call's

@@ -65,6 +65,9 @@ struct cbox
     int32_t buf_slot;
     uint64_t buf_off;
     uint64_t bstride[GHX_MAX_DIM];
+    // a field source (get plan): buf_slot is the source field's slot, buf_off the field byte offset
+    // of the source box's origin and bstride the source field's byte strides
+    bool field_src;
 };
 
 struct slot_boxes
@@ -72,7 +75,26 @@ struct slot_boxes
     const ghx_field_desc* desc = nullptr;
     int32_t dtype = 0;
     std::vector<cbox> sum, zero;
+    std::vector<cbox> src;       // the source boxes that lie in this slot's field (get plan)
+    std::vector<char> zero_is_src;  // per zero box: its entry is a contribution's source
 };
+
+bool meet(const cbox& a, const cbox& b, int spatial)
+{
+    bool m = true;
+    for (int d = 0; m && d < spatial; ++d) m = a.first[d] <= b.last[d] && b.first[d] <= a.last[d];
+    return m;
+}
+
+bool same_boxes(const ghx_pack_entry& a, const ghx_pack_entry& b)
+{
+    if (a.field_slot != b.field_slot || a.n_boxes != b.n_boxes) return false;
+    const int spatial = a.field.dim - (a.field.has_components ? 1 : 0);
+    for (int k = 0; k < a.n_boxes; ++k)
+        for (int d = 0; d < spatial; ++d)
+            if (a.boxes[k].first[d] != b.boxes[k].first[d] || a.boxes[k].last[d] != b.boxes[k].last[d]) return false;
+    return true;
+}
 
 constexpr uint64_t kMaxRecords = 0xffffffffull;  // source and tile indices are 32-bit
 }  // namespace
@@ -84,14 +106,18 @@ saccum_plan::tables::~tables()
 }
 
 saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, int n, const ghx_pack_entry* zero,
-                         int n_zero)
+                         int n_zero, const ghx_pack_entry* const* source)
+    : get(source != nullptr)
 {
     std::map<int32_t, slot_boxes> slots;
-    auto add_entry = [&](const ghx_pack_entry& en, uint32_t e, bool is_zero) {
+    enum { k_sum, k_zero, k_src };
+    // kind k_sum with `paired`: the entry's contributions come from a source field, not its buffer
+    auto add_entry = [&](const ghx_pack_entry& en, uint32_t e, int kind, bool paired = false) {
         const ghx_field_desc& f = en.field;
+        const bool is_zero = kind == k_zero, buffered = kind == k_sum && !paired;
         validate_field(f);
-        if (en.field_slot < 0 || (!is_zero && en.buffer_slot < 0)) throw invalid("negative slot");
-        if (en.field_slot >= GHX_MAX_SLOTS || (!is_zero && en.buffer_slot >= GHX_MAX_SLOTS))
+        if (en.field_slot < 0 || (buffered && en.buffer_slot < 0)) throw invalid("negative slot");
+        if (en.field_slot >= GHX_MAX_SLOTS || (buffered && en.buffer_slot >= GHX_MAX_SLOTS))
             throw invalid("an accumulate plan takes at most 64 field and 64 buffer slots (one launch)");
         if (en.n_boxes < 0 || (en.n_boxes > 0 && !en.boxes)) throw invalid("bad boxes");
         for (int d = 0; d < f.dim; ++d)
@@ -113,8 +139,9 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
             cbox c{};
             c.entry = e;
             c.box = uint32_t(b);
-            c.buf_slot = en.buffer_slot;
+            c.buf_slot = kind == k_src ? en.field_slot : en.buffer_slot;
             c.buf_off = off;
+            c.field_src = kind == k_src;
             int64_t ext[GHX_MAX_DIM];
             for (int d = 0; d < D; ++d)
             {
@@ -134,7 +161,48 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
                 bs *= uint64_t(ext[by_speed[k]]);
             }
             off += bs;
-            (is_zero ? sb.zero : sb.sum).push_back(c);
+            if (kind == k_src)
+            {
+                // where the box lies in its field, in field bytes
+                c.buf_off = 0;
+                for (int d = 0; d < D; ++d)
+                {
+                    c.buf_off += uint64_t(c.first[d] + (d < spatial ? f.offsets[d] : 0)) * uint64_t(f.byte_strides[d]);
+                    c.bstride[d] = uint64_t(f.byte_strides[d]);
+                }
+            }
+            (kind == k_src ? sb.src : is_zero ? sb.zero : sb.sum).push_back(c);
+        }
+    };
+    // contribution entry e reads box k of `src` where it would read box k of its buffer
+    auto pair_entry = [&](const ghx_pack_entry& en, uint32_t e, const ghx_pack_entry& src) {
+        const ghx_field_desc &f = en.field, &g = src.field;
+        const std::string who = "contribution entry " + std::to_string(e) + " and its source ";
+        validate_field(g);
+        if (src.n_boxes < 0 || (src.n_boxes > 0 && !src.boxes)) throw invalid("bad boxes");
+        if (en.n_boxes != src.n_boxes) throw invalid(who + "differ in their number of boxes");
+        if (f.elem_size != g.elem_size) throw invalid(who + "differ in elem_size");
+        if (f.dim != g.dim || f.num_components != g.num_components || (f.has_components != 0) != (g.has_components != 0))
+            throw invalid(who + "differ in their dimensions or components");
+        for (int d = 0; d < f.dim; ++d)
+            if (f.layout[d] != g.layout[d]) throw invalid(who + "differ in layout order");
+        const int spatial = f.dim - (f.has_components ? 1 : 0);
+        for (int b = 0; b < en.n_boxes; ++b)
+            for (int d = 0; d < spatial; ++d)
+                if (int64_t(en.boxes[b].last[d]) - en.boxes[b].first[d] != int64_t(src.boxes[b].last[d]) - src.boxes[b].first[d])
+                    throw invalid(who + "differ in the extents of box " + std::to_string(b));
+        add_entry(src, e, k_src);
+        // the entry's boxes are the last n_boxes of its slot's sums, the source's of its slot's sources
+        std::vector<cbox>& sum = slots[en.field_slot].sum;
+        const std::vector<cbox>& from = slots[src.field_slot].src;
+        for (int b = 0; b < en.n_boxes; ++b)
+        {
+            cbox& c = sum[sum.size() - size_t(en.n_boxes) + size_t(b)];
+            const cbox& q = from[from.size() - size_t(en.n_boxes) + size_t(b)];
+            c.field_src = true;
+            c.buf_slot = q.buf_slot;
+            c.buf_off = q.buf_off;
+            for (int d = 0; d < f.dim; ++d) c.bstride[d] = q.bstride[d];
         }
     };
     for (int e = 0; e < n; ++e)
@@ -145,11 +213,18 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         if (sz != en.field.elem_size)
             throw invalid("dtype code " + std::to_string(dtypes[e]) + " has " + std::to_string(sz) +
                           " bytes, the entry's elem_size is " + std::to_string(en.field.elem_size));
-        add_entry(en, uint32_t(e), false);
+        const ghx_pack_entry* src = source ? source[e] : nullptr;
+        add_entry(en, uint32_t(e), k_sum, src != nullptr);
         int32_t& dt = slots[en.field_slot].dtype;
         if (dt && dt != dtypes[e])
             throw invalid("two entries of field slot " + std::to_string(en.field_slot) + " differ in their dtype");
         dt = dtypes[e];
+        if (src)
+        {
+            pair_entry(en, uint32_t(e), *src);
+            ++n_field_sources;
+            continue;
+        }
         if (en.buffer_offset % uint64_t(sz)) throw invalid("buffer offset is not a multiple of the element size");
         max_buf_slot = std::max(max_buf_slot, en.buffer_slot);
         buf_elem[en.buffer_slot] = std::max(buf_elem[en.buffer_slot], uint8_t(sz));
@@ -159,7 +234,11 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         if (zero[k].field.elem_size != 4 && zero[k].field.elem_size != 8)
             throw invalid("a zero entry's elem_size is " + std::to_string(zero[k].field.elem_size) +
                           ", not that of a dtype (4 or 8)");
-        add_entry(zero[k], uint32_t(k), true);
+        add_entry(zero[k], uint32_t(k), k_zero);
+        bool is_src = false;
+        for (int e = 0; source && !is_src && e < n; ++e) is_src = source[e] && same_boxes(*source[e], zero[k]);
+        slot_boxes& sb = slots[zero[k].field_slot];
+        sb.zero_is_src.resize(sb.zero.size(), is_src ? 1 : 0);
     }
     // no cell is both summed and zeroed: box against box
     for (const auto& kv : slots)
@@ -168,13 +247,57 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         for (const cbox& a : kv.second.sum)
             for (const cbox& z : kv.second.zero)
             {
-                bool meet = true;
-                for (int d = 0; meet && d < spatial; ++d) meet = a.first[d] <= z.last[d] && z.first[d] <= a.last[d];
-                if (meet)
+                if (meet(a, z, spatial))
                     throw invalid("a cell of field slot " + std::to_string(kv.first) + " is both summed and zeroed (box " +
                                   std::to_string(a.box) + " of contribution entry " + std::to_string(a.entry) +
                                   " meets box " + std::to_string(z.box) + " of zero entry " + std::to_string(z.entry) + ")");
             }
+    }
+    // a get plan reads and zeroes a source cell in place: race-free only when exactly one (cell,
+    // source) pair reads it and nothing else of the launch touches it
+    for (const auto& kv : slots)
+    {
+        const slot_boxes& sb = kv.second;
+        const int spatial = sb.desc->dim - (sb.desc->has_components ? 1 : 0);
+        const std::string slot = "field slot " + std::to_string(kv.first);
+        auto name = [](const cbox& c) { return "box " + std::to_string(c.box) + " of the source of contribution entry " + std::to_string(c.entry); };
+        for (size_t i = 0; i < sb.src.size(); ++i)
+        {
+            const cbox& a = sb.src[i];
+            for (size_t j = i + 1; j < sb.src.size(); ++j)
+                if (meet(a, sb.src[j], spatial))
+                    throw invalid("two source boxes of " + slot + " meet (" + name(a) + ", " + name(sb.src[j]) + ")");
+            for (const cbox& c : sb.sum)
+                if (meet(a, c, spatial))
+                    throw invalid("a source box of " + slot + " meets a contribution box (" + name(a) + ", box " +
+                                  std::to_string(c.box) + " of contribution entry " + std::to_string(c.entry) + ")");
+            for (size_t z = 0; z < sb.zero.size(); ++z)
+                if (!sb.zero_is_src[z] && meet(a, sb.zero[z], spatial))
+                    throw invalid("a source box of " + slot + " meets a zero box (" + name(a) + ", box " +
+                                  std::to_string(sb.zero[z].box) + " of zero entry " + std::to_string(sb.zero[z].entry) + ")");
+        }
+    }
+    // the source pointer table of a get plan: the buffer slots that are read, then the source
+    // field slots; a plan without sources indexes the buffers themselves
+    int32_t tab_of_buf[GHX_MAX_SLOTS], tab_of_field[GHX_MAX_SLOTS];
+    for (int b = 0; b < GHX_MAX_SLOTS; ++b) tab_of_buf[b] = get ? -1 : b, tab_of_field[b] = -1;
+    if (get)
+    {
+        for (int b = 0; b < GHX_MAX_SLOTS; ++b)
+            if (buf_elem[b])
+            {
+                tab_of_buf[b] = int32_t(tab_slot.size());
+                tab_slot.push_back(b);
+            }
+        tab_field = uint32_t(tab_slot.size());
+        for (const auto& kv : slots)
+            if (!kv.second.src.empty())
+            {
+                tab_of_field[kv.first] = int32_t(tab_slot.size());
+                tab_slot.push_back(kv.first);
+            }
+        if (tab_slot.size() > size_t(GHX_MAX_SLOTS))
+            throw invalid("a get plan takes at most 64 source slots (the buffers it reads and its source fields, one launch)");
     }
 
     const uint32_t tb = std::max<uint32_t>(1, g_tune.tile_bytes);
@@ -197,7 +320,8 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         const uint32_t first_src = uint32_t(srcs.size());
         // rows along the layout's fastest dim; a strided fastest dim makes every element a row
         const int cont = by_speed[0];
-        const bool unit = f.byte_strides[cont] == elem;
+        bool unit = f.byte_strides[cont] == elem;
+        for (uint32_t j : list) unit = unit && from[j].bstride[cont] == uint64_t(elem);  // a strided source field
         int64_t L = unit ? ext[cont] * elem : elem;
         int outer[GHX_MAX_DIM];
         int n_outer = 0;
@@ -236,14 +360,15 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
             sacc_src s{};
             s.buf_off = c.buf_off;
             for (int d = 0; d < spatial; ++d) s.buf_off += uint64_t(lo[d] - c.first[d]) * c.bstride[d];
-            s.buf_slot = uint32_t(c.buf_slot);
+            s.buf_slot = uint32_t(c.field_src ? tab_of_field[c.buf_slot] : tab_of_buf[c.buf_slot]);
+            s.flags = c.field_src ? kSaccFieldSrc : 0;
             w = std::min(w, wlog2_of(s.buf_off));
             for (int k = 0; k < n_outer; ++k)
             {
                 s.stride[k] = c.bstride[outer[k]];
                 w = std::min(w, wlog2_of(s.stride[k]));
             }
-            t.buf_mask |= uint64_t(1) << c.buf_slot;
+            t.buf_mask |= uint64_t(1) << s.buf_slot;
             srcs.push_back(s);
             src_entry.push_back(c.entry);
             src_box.push_back(c.box);
@@ -366,7 +491,9 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
     n_sum_boxes = uint32_t(boxes.size());
     n_sum_tiles = uint32_t(tiles.size());
     for (const auto& kv : slots)
-        for (const cbox& z : kv.second.zero) emit(kv.first, kv.second, z.first, z.last, kv.second.zero, {}, true);
+        for (size_t z = 0; z < kv.second.zero.size(); ++z)
+            if (!kv.second.zero_is_src[z])
+                emit(kv.first, kv.second, kv.second.zero[z].first, kv.second.zero[z].last, kv.second.zero, {}, true);
 
     if (tiles.empty() || !have_device()) return;
     to_device(dev.tiles, tiles, "accumulate tiles");
@@ -376,6 +503,7 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
 int saccum_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const
 {
     const uint32_t n_tiles = zero_halos ? uint32_t(tiles.size()) : n_sum_tiles;
+    if (get) throw invalid("a get plan (ghx_saccum_get_create) runs through ghx_saccum_get_execute");
     if (n_tiles == 0) return GHX_OK;
     if (!fptr || (!bptr && max_buf_slot >= 0) || nf <= max_field_slot || nb <= max_buf_slot)
         throw invalid("pointer arrays do not cover the plan's slots");
@@ -401,6 +529,43 @@ int saccum_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, b
     a.tiles = static_cast<const sacc_tile*>(dev.tiles);
     a.srcs = static_cast<const sacc_src*>(dev.srcs);
     return launch_accum_s(a, stream, grid_for_tiles(n_tiles));
+}
+
+// k_accum_get_s: the source pointer table holds the buffers that are read, then the source fields
+int saccum_plan::execute_get(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const
+{
+    if (!get) throw invalid("not a get plan (ghx_saccum_get_create)");
+    const uint32_t n_tiles = zero_halos ? uint32_t(tiles.size()) : n_sum_tiles;
+    if (n_tiles == 0) return GHX_OK;
+    if (!fptr || (!bptr && max_buf_slot >= 0) || nf <= max_field_slot || nb <= max_buf_slot)
+        throw invalid("pointer arrays do not cover the plan's slots");
+    kargs_sa a{};
+    a.n_tiles = n_tiles;
+    a.zero_src = zero_halos ? 1 : 0;
+    for (int s = 0; s <= max_field_slot; ++s)
+    {
+        if (!slot_elem[s]) continue;
+        if (!fptr[s]) throw invalid("null field pointer");
+        a.field_ptr[s] = reinterpret_cast<uint64_t>(fptr[s]);
+        if (a.field_ptr[s] % slot_elem[s]) throw invalid("a field pointer is not aligned to its element");
+    }
+    for (uint32_t t = 0; t < uint32_t(tab_slot.size()); ++t)
+    {
+        const int32_t s = tab_slot[t];
+        if (t >= tab_field) a.buf_ptr[t] = a.field_ptr[s];  // checked above
+        else
+        {
+            if (!bptr[s]) throw invalid("null buffer pointer");
+            a.buf_ptr[t] = reinterpret_cast<uint64_t>(bptr[s]);
+            if (a.buf_ptr[t] % buf_elem[s]) throw invalid("a buffer pointer is not aligned to its elements");
+        }
+        if (a.buf_ptr[t] % 8) a.buf_mis8 |= uint64_t(1) << t;
+        if (a.buf_ptr[t] % 16) a.buf_mis16 |= uint64_t(1) << t;
+    }
+    if (!dev.tiles) throw hip_error("plan has no device tables (no HIP device at creation)");
+    a.tiles = static_cast<const sacc_tile*>(dev.tiles);
+    a.srcs = static_cast<const sacc_src*>(dev.srcs);
+    return launch_accum_get_s(a, stream, grid_for_tiles(n_tiles));
 }
 
 }  // namespace ghx

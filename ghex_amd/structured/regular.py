@@ -15,6 +15,11 @@ from .cartesian_sets import IndexSpace, ProductSet, UnitRange, union  # noqa: F4
 
 
 def make_communication_object(context, **options) -> CommunicationObject:
+    """The plain communication object. adjoint_boxes=True (opt-in): adjoint_exchange and its
+    siblings take regular structured fields. fuse_adjoint=True (opt-in, with adjoint_boxes): the
+    adjoint adds the halo cells of self messages straight into their owner cells in the
+    accumulate launch (ghx_sexchange_adjoint_self_*); their buffers are not touched. An exchange
+    without a self message takes the usual path."""
     return CommunicationObject(context, **options)
 
 

@@ -1045,6 +1045,39 @@ int ghx_saccum_source(const ghx_saccum* p, int64_t j, int32_t* entry, int32_t* b
                       int32_t* buffer_slot, uint64_t* buffer_offset_of_origin);
 int ghx_saccum_destroy(ghx_saccum* p);
 
+/* The get-accumulate (k_accum_get_s): ghx_saccum_create's operation, S[send cell] += R[recv cell] in
+ * ascending (entry, box), where a contribution entry may read R where it lies — the halo cells of a
+ * receiving field of the same launch — instead of a buffer. source[e], e < n, is the halo side of
+ * contribution entry e's message (field slot, descriptor and boxes; buffer members ignored; box k
+ * pairs with box k) or NULL: the entry reads its buffer as in ghx_saccum_create. Source records
+ * then hold the field byte offset of the sub-box's origin in the source field and that field's
+ * byte strides; the cutting, the merging, the list order and the record layout stay (a sub-box
+ * whose fastest dimension is strided in a source field takes single elements as rows). A sub-box's
+ * list may mix both kinds. zero[k] as in ghx_saccum_create, but a zero entry that is a
+ * contribution's source (same field slot, same boxes) gets no zero tiles: with zero_halos the lane
+ * that loaded a halo vector stores zero bytes over it. That is race-free because the planner
+ * verifies, and refuses otherwise, that every source cell is read by one (cell, source) pair and
+ * touched by nothing else. ghx_saccum_execute's field_ptrs serve both sides; buffer_ptrs need cover
+ * only the slots of entries without a source. ghx_saccum_info / _box / _source / _destroy work on
+ * the plan (_source's buffer_slot is then the record's index in the launch's source pointer table:
+ * the buffer slots that are read, ascending, then the source field slots, ascending);
+ * ghx_saccum_execute refuses it, as ghx_saccum_get_execute refuses a plan of ghx_saccum_create.
+ * GHX_ERR_INVALID, with the reason, for ghx_saccum_create's reasons and when: an entry and its
+ * source differ in their number of boxes, in a box's extents, in elem_size, dimensions,
+ * components or layout order; two source boxes of one field slot meet; a source box meets a
+ * contribution box, or a zero box of an entry that is no source, of the same field slot; the source
+ * pointer table would hold more than 64 slots. */
+int ghx_saccum_get_create(const ghx_pack_entry* contrib, const int32_t* dtypes,
+                          const ghx_pack_entry* const* source, int32_t n, const ghx_pack_entry* zero,
+                          int32_t n_zero, ghx_saccum** out);
+int ghx_saccum_get_execute(const ghx_saccum* p, void* const* field_ptrs, int32_t n_fields,
+                           void* const* buffer_ptrs, int32_t n_buffers, int32_t zero_halos,
+                           ghx_stream stream);
+/* Source record j (host only, any plan): kind 0 = a buffer, 1 = a field source; the buffer slot or
+ * the source field's slot; the byte offset there of the cell at the sub-box's origin. */
+int ghx_saccum_source_kind(const ghx_saccum* p, int64_t j, int32_t* kind, int32_t* slot,
+                           uint64_t* offset_of_origin);
+
 /* The adjoint of an exchange of regular structured items, the twin of ghx_uexchange_adjoint_*:
  * create attaches the reverse pack (a ghx_plan of direction 0 over the exchange's unpack entries)
  * and the accumulate plan (pack entries as contribution entries, unpack entries as zero entries);
@@ -1061,6 +1094,30 @@ int ghx_sexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, 
 int ghx_sexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
                                      int32_t n_fields, void* const* send_buffers, int32_t n_send,
                                      int32_t zero_halos, ghx_stream stream);
+
+/* The same adjoint with the self messages fused: a message whose receiver is a field of this rank
+ * (the pairing of ghx_exchange_pack_self: a receive buffer of this rank with a send buffer of the
+ * same pair of domains and size) is accumulated straight from the receiving field's halo cells, and
+ * its buffer is neither written nor read. self_create attaches a get plan (ghx_saccum_get_create:
+ * every send entry of a self message sourced by the receive entry at the same message bytes) and,
+ * where peer messages remain, a reverse pack over the peer receive entries alone — those
+ * ghx_exchange_unpack_peers covers. It refuses what ghx_sexchange_adjoint_create refuses, an
+ * exchange with no self message, and a self message whose two sides do not pair; it leaves the
+ * plans of ghx_sexchange_adjoint_create alone. self_info works on any exchange: form 0 = none,
+ * 1 = every message is a self message, 2 = mixed; sum sub-boxes, source records and how many
+ * contribution entries have a field source. self_pack has ghx_sexchange_adjoint_pack's argument
+ * contract: form 1 launches nothing and returns GHX_OK, form 2 gathers the peer messages' halo
+ * cells into their receive buffers. self_accumulate has ghx_sexchange_adjoint_accumulate's: one
+ * k_accum_get_s launch, self messages from the halos, peer messages from the send buffers. */
+int ghx_sexchange_adjoint_self_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items);
+int ghx_sexchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64_t* n_boxes,
+                                    int64_t* n_sources, int64_t* n_field_sources);
+int ghx_sexchange_adjoint_self_pack(const ghx_exchange* ex, void* const* field_ptrs,
+                                    int32_t n_fields, void* const* recv_buffers, int32_t n_recv,
+                                    ghx_stream stream);
+int ghx_sexchange_adjoint_self_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
+                                          int32_t n_fields, void* const* send_buffers,
+                                          int32_t n_send, int32_t zero_halos, ghx_stream stream);
 
 /* The adjoint of a cubed-sphere exchange (ghx_cs_exchange_create), the third twin. The forward
  * unpack sets R[x, y, z, k] = s_k * B[T(x, y), z, k] (B the dense box in the neighbour tile's
