@@ -193,6 +193,13 @@ _SIGS = {
     "ghx_cs_exchange_adjoint_segments": (c_i32, [c_vp, P(c_i32), P(c_i32)]),
     "ghx_cs_exchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
     "ghx_cs_exchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
+    "ghx_cs_exchange_adjoint_self_create": (c_i32, [c_vp, P(c_i32), c_i32]),
+    "ghx_cs_exchange_adjoint_self_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
+    "ghx_cs_exchange_adjoint_self_plan": (c_i32, [c_vp, P(c_vp)]),
+    "ghx_cs_exchange_adjoint_self_segments": (c_i32, [c_vp, P(c_i32), P(c_i32)]),
+    "ghx_saccum_source_map": (c_i32, [c_vp, c_i64, P(c_i64), P(c_i32), P(c_i32)]),
+    "ghx_cs_exchange_adjoint_self_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
+    "ghx_cs_exchange_adjoint_self_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
                               c_i32, c_vp]),
     "ghx_cs_pack_rotated": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),

@@ -254,7 +254,7 @@ class CommunicationObject:
                  direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False,
                  fuse_lists: bool = False, fuse_lists_mixed: bool = False,
                  adjoint_boxes: bool = False, adjoint_rotated: bool = False,
-                 fuse_adjoint: bool = False):
+                 fuse_adjoint: bool = False, fuse_adjoint_rotated: bool = False):
         if staging not in (None, "host"):
             raise ValueError("staging must be None (device buffers) or 'host'")
         if direct and (staging is not None or pipelined or rccl_self):
@@ -301,6 +301,13 @@ class CommunicationObject:
             raise ValueError("fuse_adjoint fuses the adjoint of regular structured fields: it needs "
                              "adjoint_boxes=True")
         self.fuse_adjoint = bool(fuse_adjoint)
+        # the same for cubed-sphere fields: a self message's halo cells are read through the edge's
+        # transform, negated where it negates (ghx_cs_exchange_adjoint_self_*, k_accum_get_x).
+        # Opt-in, with adjoint_rotated; a plan without a self message takes the usual path
+        if fuse_adjoint_rotated and not adjoint_rotated:
+            raise ValueError("fuse_adjoint_rotated fuses the adjoint of cubed-sphere fields: it "
+                             "needs adjoint_rotated=True")
+        self.fuse_adjoint_rotated = bool(fuse_adjoint_rotated)
         self.staging = staging
         self.pipelined = pipelined
         # tests: route the self messages through RCCL too (a 1-rank communicator), so the
@@ -588,7 +595,9 @@ class CommunicationObject:
         """The plan of `bis` with its adjoint plans attached (built on first use): the reverse
         pack and the accumulate (ghx_uexchange_adjoint_create, k_accum_u; with adjoint_boxes and
         regular structured fields ghx_sexchange_adjoint_create, k_accum_s; with adjoint_rotated
-        and cubed-sphere fields ghx_cs_exchange_adjoint_create, k_pack_x and k_accum_s)."""
+        and cubed-sphere fields ghx_cs_exchange_adjoint_create, k_pack_x and k_accum_s; with
+        fuse_adjoint_rotated and a self message ghx_cs_exchange_adjoint_self_create,
+        k_accum_get_x)."""
         if self.direct or self.pipelined:
             raise ValueError("the adjoint exchange is the plain communication object's "
                              "(no direct=True, no pipelined=True)")
@@ -597,6 +606,11 @@ class CommunicationObject:
             if not all(rotated):
                 raise ValueError("an exchange takes cubed-sphere fields or other fields, "
                                  "not both")
+            if self.fuse_adjoint_rotated and self.fuse_self:
+                me = self.context.rank()
+                if any(x["rank"] == me for x in self.plan(bis).recv):
+                    # all self or mixed: the self messages come from the halos (k_accum_get_x)
+                    return self._with_adjoint(bis, "ghx_cs_exchange_adjoint_self_")
             return self._with_adjoint(bis, "ghx_cs_exchange_adjoint_")
         boxes = self.adjoint_boxes and any(
             bi.field.kind != 1 or getattr(bi.field, "cs_item", None) is not None for bi in bis)
@@ -640,7 +654,9 @@ class CommunicationObject:
         fuse_self), regular structured fields whose plan has a self message take the fused form:
         the reverse pack gathers the peer messages only, the transport carries them as before,
         and the accumulate reads the self messages from the halo cells themselves. The send and
-        receive buffers of self messages are then not touched: they keep whatever they held."""
+        receive buffers of self messages are then not touched: they keep whatever they held.
+        fuse_adjoint_rotated=True (with adjoint_rotated and fuse_self) is the same for
+        cubed-sphere fields: a self message's halo cells are read through the edge's transform."""
         import torch
         bis = self._as_list(buffer_infos)
         stream = torch.cuda.current_stream(bis[0].field.device.index) if bis else None

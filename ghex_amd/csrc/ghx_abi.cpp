@@ -1669,6 +1669,106 @@ int ghx_cs_exchange_adjoint_accumulate(const ghx_exchange* ex, void* const* fiel
     });
 }
 
+int ghx_cs_exchange_adjoint_self_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        ex->make_cs_adjoint_self(dtypes, n_items);
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_exchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64_t* n_boxes, int64_t* n_sources,
+                                      int64_t* n_field_sources, int64_t* n_rotated_sources)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(form, "form");
+        const saccum_plan* p = ex->cs_self_accum.get();
+        *form = p ? ex->cs_self_form : 0;
+        if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
+        if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
+        if (n_field_sources) *n_field_sources = p ? int64_t(p->n_field_sources) : 0;
+        if (n_rotated_sources) *n_rotated_sources = p ? int64_t(p->n_rotated_sources) : 0;
+        return GHX_OK;
+    });
+}
+
+namespace
+{
+void check_cs_adjoint_self(const ghx_exchange* ex)
+{
+    check_ptr(ex, "exchange");
+    if (!ex->cs_self_accum)
+        throw invalid("fused cubed-sphere adjoint exchange: no plans (ghx_cs_exchange_adjoint_self_create)");
+    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
+}
+}  // namespace
+
+int ghx_cs_exchange_adjoint_self_plan(const ghx_exchange* ex, const ghx_saccum** out)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(out, "out");
+        if (!ex->cs_self_accum)
+            throw invalid("fused cubed-sphere adjoint exchange: no plans (ghx_cs_exchange_adjoint_self_create)");
+        *out = ex->cs_self_accum.get();
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_exchange_adjoint_self_segments(const ghx_exchange* ex, int32_t* n_pack_segments, int32_t* n_pack_x_records)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        if (n_pack_segments) *n_pack_segments = ex->cs_self_pack ? ex->cs_self_pack->n_segments : 0;
+        if (n_pack_x_records) *n_pack_x_records = ex->cs_self_xpack ? ex->cs_self_xpack->n_records : 0;
+        return GHX_OK;
+    });
+}
+
+int ghx_saccum_source_map(const ghx_saccum* p, int64_t j, int64_t* strides, int32_t* neg_mask, int32_t* comp_dim)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (j < 0 || uint64_t(j) >= p->srcs.size()) throw invalid("source index out of range");
+        const saccum_plan::source_map& m = p->src_map[size_t(j)];
+        for (int d = 0; strides && d < GHX_MAX_DIM; ++d) strides[d] = m.stride[d];
+        if (neg_mask) *neg_mask = m.neg;
+        if (comp_dim) *comp_dim = m.comp_dim;
+        return GHX_OK;
+    });
+}
+
+int ghx_cs_exchange_adjoint_self_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                      void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
+{
+    return guarded([&] {
+        check_cs_adjoint_self(ex);
+        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
+        // every message a self message: nothing to gather. Else the peer receive spaces alone, the
+        // transformed ones after the ordinary launch on the same stream
+        int rc = GHX_OK;
+        if (ex->cs_self_pack) rc = ex->cs_self_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+        if (rc == GHX_OK && ex->cs_self_xpack)
+            rc = ex->cs_self_xpack->execute_pack(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+        return rc;
+    });
+}
+
+int ghx_cs_exchange_adjoint_self_accumulate(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                            void* const* send_buffers, int32_t n_send, int32_t zero_halos,
+                                            ghx_stream stream)
+{
+    return guarded([&] {
+        check_cs_adjoint_self(ex);
+        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
+        return ex->cs_self_accum->execute_get(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
+    });
+}
+
 int ghx_uput_segment(const ghx_put* put, int32_t k, ghx_uput_segment_info* out)
 {
     return guarded([&] {

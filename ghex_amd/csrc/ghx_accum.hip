@@ -1,5 +1,6 @@
 // ghx_accum.hip — gfx950 (CDNA4) adjoint accumulate for index-list halos (k_accum_u) and, further
-// down, for structured fields (k_accum_s).
+// down, for structured fields (k_accum_s, its get form k_accum_get_s and the cubed sphere's
+// k_accum_get_x).
 //
 // The adjoint of the halo exchange sends every halo copy of a cell back to the cell's owner and
 // sums it there. The contributions are already stored once: they are the message bytes a reverse
@@ -220,10 +221,14 @@ __device__ __forceinline__ GHX_GLOBAL V* src_addr(const kargs_sa& a, const GHX_C
 
 // the loads of N sources from record j on, issued together; then, in a launch with zero_halos, zero
 // bytes over those that are field sources (a wave-uniform branch per source: the flags come from the
-// scalar path), each by the lane that loaded it; then the adds, in list order
-template<typename V, int N>
+// scalar path), each by the lane that loaded it; then the adds, in list order. Signed
+// (k_accum_get_x): a source whose flags carry the bit `sel` — the lane's component, one for the
+// whole vector — is negated before its add: a sign-bit flip for floats, two's complement for
+// integers (negate_elem's, ghx_kernels.hip), so the sum's bits are those of adding the buffer cell
+// the rotating reverse pack would have stored
+template<typename V, int N, bool Signed>
 __device__ __forceinline__ V get_batch(const kargs_sa& a, const GHX_CONST sacc_src* srcs, uint32_t j,
-                                       const uint32_t (&c)[4], uint32_t col, bool deep, V acc)
+                                       const uint32_t (&c)[4], uint32_t col, bool deep, V acc, uint32_t sel)
 {
     GHX_GLOBAL V* p[N];
     uint32_t fl[N];
@@ -238,11 +243,15 @@ __device__ __forceinline__ V get_batch(const kargs_sa& a, const GHX_CONST sacc_s
     for (uint32_t k = 0; k < uint32_t(N); ++k)
         if (a.zero_src & fl[k]) *p[k] = V(0);
 #pragma unroll
-    for (uint32_t k = 0; k < uint32_t(N); ++k) acc = acc + v[k];
+    for (uint32_t k = 0; k < uint32_t(N); ++k)
+    {
+        if constexpr (Signed) acc = acc + ((fl[k] & sel) ? -v[k] : v[k]);
+        else acc = acc + v[k];
+    }
     return acc;
 }
 
-template<typename T, int W, bool Get = false>
+template<typename T, int W, bool Get = false, bool Signed = false>
 __device__ __forceinline__ void accum_tile_s(const kargs_sa& a, const sacc_tile& s, const GHX_CONST sacc_src* srcs)
 {
     typedef typename vec_of<T, W / int(sizeof(T))>::type V;
@@ -261,11 +270,25 @@ __device__ __forceinline__ void accum_tile_s(const kargs_sa& a, const sacc_tile&
         uint32_t j = s.first_src, left = s.n_src;  // uniform
         if constexpr (Get)
         {
+            // the flags bit of the lane's component (components 0 and 1 alone change sign); where
+            // the row is the vector of components the planner has made the lanes take elements
+            uint32_t sel = 0;
+            if constexpr (Signed)
+            {
+                const uint32_t c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];  // selects, no indexing
+                const uint32_t ci = s.comp == kSaccCompNone  ? 0u
+                                    : s.comp == kSaccCompRow ? col / uint32_t(sizeof(T))
+                                    : s.comp == 1            ? c0
+                                    : s.comp == 2            ? c1
+                                    : s.comp == 3            ? c2
+                                                             : c3;
+                sel = ci < 2u ? (1u << kSaccNegShift) << ci : 0u;
+            }
             for (; left >= uint32_t(kAccBatch); j += kAccBatch, left -= kAccBatch)
-                acc = get_batch<V, kAccBatch>(a, srcs, j, c, col, deep, acc);
-            if (left == 3) acc = get_batch<V, 3>(a, srcs, j, c, col, deep, acc);
-            else if (left == 2) acc = get_batch<V, 2>(a, srcs, j, c, col, deep, acc);
-            else if (left == 1) acc = get_batch<V, 1>(a, srcs, j, c, col, deep, acc);
+                acc = get_batch<V, kAccBatch, Signed>(a, srcs, j, c, col, deep, acc, sel);
+            if (left == 3) acc = get_batch<V, 3, Signed>(a, srcs, j, c, col, deep, acc, sel);
+            else if (left == 2) acc = get_batch<V, 2, Signed>(a, srcs, j, c, col, deep, acc, sel);
+            else if (left == 1) acc = get_batch<V, 1, Signed>(a, srcs, j, c, col, deep, acc, sel);
             *cell = acc;
             continue;
         }
@@ -316,16 +339,16 @@ __device__ __forceinline__ void zero_tile_s(const kargs_sa& a, const sacc_tile& 
     }
 }
 
-template<typename T, bool Get = false>
+template<typename T, bool Get = false, bool Signed = false>
 __device__ __forceinline__ void accum_tile_sw(const kargs_sa& a, const sacc_tile& s, const GHX_CONST sacc_src* srcs, int w)
 {
-    if (w == 4) accum_tile_s<T, 16, Get>(a, s, srcs);
-    else if constexpr (sizeof(T) == 8) accum_tile_s<T, 8, Get>(a, s, srcs);
-    else if (w == 3) accum_tile_s<T, 8, Get>(a, s, srcs);
-    else accum_tile_s<T, 4, Get>(a, s, srcs);
+    if (w == 4) accum_tile_s<T, 16, Get, Signed>(a, s, srcs);
+    else if constexpr (sizeof(T) == 8) accum_tile_s<T, 8, Get, Signed>(a, s, srcs);
+    else if (w == 3) accum_tile_s<T, 8, Get, Signed>(a, s, srcs);
+    else accum_tile_s<T, 4, Get, Signed>(a, s, srcs);
 }
 
-template<bool Get>
+template<bool Get, bool Signed = false>
 __device__ __forceinline__ void accum_tiles_s(const kargs_sa& a)
 {
     const GHX_CONST sacc_tile* tiles = (const GHX_CONST sacc_tile*)reinterpret_cast<uintptr_t>(a.tiles);
@@ -340,10 +363,10 @@ __device__ __forceinline__ void accum_tiles_s(const kargs_sa& a)
             else if (w == 3) zero_tile_s<8>(a, s);
             else zero_tile_s<4>(a, s);
         }
-        else if (s.dtype == GHX_DT_F32) accum_tile_sw<float, Get>(a, s, srcs, w);
-        else if (s.dtype == GHX_DT_F64) accum_tile_sw<double, Get>(a, s, srcs, w);
-        else if (s.dtype == GHX_DT_I64) accum_tile_sw<uint64_t, Get>(a, s, srcs, w);
-        else accum_tile_sw<uint32_t, Get>(a, s, srcs, w);
+        else if (s.dtype == GHX_DT_F32) accum_tile_sw<float, Get, Signed>(a, s, srcs, w);
+        else if (s.dtype == GHX_DT_F64) accum_tile_sw<double, Get, Signed>(a, s, srcs, w);
+        else if (s.dtype == GHX_DT_I64) accum_tile_sw<uint64_t, Get, Signed>(a, s, srcs, w);
+        else accum_tile_sw<uint32_t, Get, Signed>(a, s, srcs, w);
     }
 }
 
@@ -354,6 +377,16 @@ __global__ __launch_bounds__(kBlock) void k_accum_s(kargs_sa a) { accum_tiles_s<
 // verified that one (cell, source) pair reads a halo cell and that nothing else touches it, so the
 // lane that loaded a halo vector may store zero bytes over it (zero_halos) with no other ordering.
 __global__ __launch_bounds__(kBlock) void k_accum_get_s(kargs_sa a) { accum_tiles_s<true>(a); }
+
+// k_accum_get_x: k_accum_get_s's walk for a cubed-sphere exchange. A self message's source is the
+// halo cell whose image under the edge's transform the owner cell is: its record holds the image of
+// the sub-box's origin and signed byte strides (mod 2^64, so the same unsigned products address it),
+// and in its flags the vector components the edge negates. A transposed or reversed source has made
+// the planner cut the rows into elements, a lane then walks the owner field in order and the halo
+// across it; a vector (z- or component-fastest rows) has one component or, where the row is the
+// components, one element per lane, so one sign serves a lane's whole vector. Its own instantiation:
+// k_accum_s and k_accum_get_s compile as they did.
+__global__ __launch_bounds__(kBlock) void k_accum_get_x(kargs_sa a) { accum_tiles_s<true, true>(a); }
 
 template<typename K>
 int launch_sa(K kernel, const char* what, const kargs_sa& a, void* stream, uint32_t grid)
@@ -381,6 +414,11 @@ int launch_sa(K kernel, const char* what, const kargs_sa& a, void* stream, uint3
     return GHX_OK;
 }
 }  // namespace
+
+int launch_accum_get_x(const kargs_sa& a, void* stream, uint32_t grid)
+{
+    return launch_sa(k_accum_get_x, "cubed-sphere adjoint get-accumulate", a, stream, grid);
+}
 
 int launch_accum_get_s(const kargs_sa& a, void* stream, uint32_t grid)
 {

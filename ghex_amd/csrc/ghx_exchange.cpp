@@ -726,6 +726,12 @@ std::unique_ptr<ghx_exchange> make_exchange(const ghx_exchange_item* items, cons
             ex->cs_gf = rp.gf;
             ex->cs_gb = rp.gb;
             ex->cs_sbytes = rp.sbytes;
+            for (const halo_entry* he : halos)  // for the fused adjoint (make_cs_adjoint_self)
+            {
+                ex->cs_rhalos.emplace_back();
+                ex->cs_rhalos.back().boxes = he->boxes;
+                ex->cs_rhalos.back().tiles = he->tiles;
+            }
             if (!rp.segs.empty())
                 ex->sunpack = std::make_unique<splan>(std::move(rp.segs), rp.gf, rp.gb, rp.sbytes, 1);
             if (!rp.xs.empty()) ex->xunpack = std::make_unique<xplan>(std::move(rp.xs));
@@ -906,12 +912,18 @@ void exchange_plan::make_sadjoint_self(const int32_t* dtypes, int32_t n)
     sself_pack = std::move(pack);
 }
 
-void exchange_plan::make_cs_adjoint(const int32_t* dtypes, int32_t n)
+namespace
 {
-    if (!cubed_sphere)
+// what both cubed-sphere adjoint creates refuse of their arguments
+void check_cs_adjoint_args(const exchange_plan& ex, const int32_t* dtypes, int32_t n)
+{
+    const int32_t n_items = ex.n_items;
+    const std::vector<int32_t>& cs_elem = ex.cs_elem;
+    const std::vector<ghx_cs_item>& cs_items = ex.cs_items;
+    if (!ex.cubed_sphere)
         throw invalid("cubed-sphere adjoint exchange: not a cubed-sphere exchange (regular structured items take "
                       "ghx_sexchange_adjoint_create, index-list items ghx_uexchange_adjoint_create)");
-    if (dir_parity[0].word || dir_parity[1].word)
+    if (ex.dir_parity[0].word || ex.dir_parity[1].word)
         throw invalid("adjoint exchange: the exchange has double-buffered buffers "
                       "(ghx_exchange_set_parity); its launches use one copy");
     if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
@@ -931,6 +943,12 @@ void exchange_plan::make_cs_adjoint(const int32_t* dtypes, int32_t n)
                           std::to_string(cs_items[size_t(i)].value_kind) + " but dtype code " +
                           std::to_string(dtypes[i]) + " (1: GHX_DT_F32 / _F64, 2: GHX_DT_I32 / _I64)");
     }
+}
+}  // namespace
+
+void exchange_plan::make_cs_adjoint(const int32_t* dtypes, int32_t n)
+{
+    check_cs_adjoint_args(*this, dtypes, n);
     std::vector<int32_t> dt;
     for (const ghx_pack_entry& e : entries[0]) dt.push_back(dtypes[e.field_slot]);
     auto accum = std::make_unique<::ghx_saccum>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
@@ -940,6 +958,92 @@ void exchange_plan::make_cs_adjoint(const int32_t* dtypes, int32_t n)
     cs_adj_accum = std::move(accum);
     cs_adj_pack = std::move(pack);
     cs_adj_ready = true;
+}
+
+void exchange_plan::make_cs_adjoint_self(const int32_t* dtypes, int32_t n)
+{
+    check_cs_adjoint_args(*this, dtypes, n);
+    // the receive entry at the same message bytes sources a self message's send entry (the match
+    // of make_sadjoint_self), box k of one with box k of the other as build_cs_self pairs them
+    std::vector<int> recv_of_send(send.size(), -1);
+    for (size_t j = 0; j < send_of_recv.size(); ++j)
+        if (send_of_recv[j] >= 0) recv_of_send[size_t(send_of_recv[j])] = int(j);
+    std::vector<int32_t> dt;
+    std::vector<const ghx_pack_entry*> source;
+    std::vector<std::vector<xseg>> spaces(entries[0].size());
+    std::vector<const xseg*> space;
+    std::vector<char> sourced(entries[1].size(), 0);
+    size_t n_self = 0;
+    for (size_t e = 0; e < entries[0].size(); ++e)
+    {
+        const ghx_pack_entry& se = entries[0][e];
+        dt.push_back(dtypes[se.field_slot]);
+        source.push_back(nullptr);
+        space.push_back(nullptr);
+        const int j = recv_of_send[size_t(se.buffer_slot)];
+        if (j < 0) continue;
+        size_t k = 0;
+        for (; k < entries[1].size(); ++k)
+            if (entries[1][k].buffer_slot == j && entries[1][k].buffer_offset == se.buffer_offset) break;
+        if (k == entries[1].size())
+            throw invalid("fused adjoint: a send entry of a self message has no receive entry at the same "
+                          "message bytes");
+        const ghx_pack_entry& re = entries[1][k];
+        const halo_entry& he = cs_rhalos[k];
+        if (int(he.boxes.size()) != re.n_boxes || re.n_boxes != se.n_boxes)
+            throw invalid("fused adjoint: contribution entry " + std::to_string(e) +
+                          " and its source differ in their number of boxes");
+        for (size_t b = 0; b < he.boxes.size(); ++b)
+            spaces[e].push_back(cs_space_box(re.field, cs_items[size_t(re.field_slot)], he.boxes[b], he.tiles[b],
+                                             re.field_slot, re.buffer_slot, 0));
+        source.back() = &re;
+        space.back() = spaces[e].data();
+        sourced[k] = 1;
+        ++n_self;
+    }
+    if (n_self == 0)
+        throw invalid("fused adjoint: the exchange has no self message (ghx_cs_exchange_adjoint_create)");
+    std::vector<char> peer_buf(recv.size(), 0);
+    bool any_peer = false;
+    for (size_t k = 0; k < entries[1].size(); ++k)
+    {
+        if (sourced[k]) continue;
+        if (send_of_recv[size_t(entries[1][k].buffer_slot)] >= 0)
+            throw invalid("fused adjoint: a receive entry of a self message has no send entry at the same "
+                          "message bytes");
+        peer_buf[size_t(entries[1][k].buffer_slot)] = 1;
+        any_peer = true;
+    }
+    auto accum = std::make_unique<::ghx_saccum>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
+                                               int(entries[1].size()), source.data(), space.data());
+    // the reverse pack of the peer receive spaces: the kept ordinary segments and the transformed
+    // boxes whose receive buffer is a peer's
+    std::unique_ptr<splan> pack;
+    std::unique_ptr<xplan> xpack;
+    if (any_peer)
+    {
+        std::vector<seg_s> segs;
+        std::vector<int32_t> gf, gb;
+        uint64_t bytes = 0;
+        for (size_t i = 0; i < cs_segs.size(); ++i)
+            if (peer_buf[size_t(cs_gb[i])])
+            {
+                segs.push_back(cs_segs[i]);
+                gf.push_back(cs_gf[i]);
+                gb.push_back(cs_gb[i]);
+                bytes += cs_segs[i].bytes;
+            }
+        if (!segs.empty()) pack = std::make_unique<splan>(std::move(segs), gf, gb, bytes, 0);
+        std::vector<xseg> boxes;
+        if (xunpack)
+            for (const xseg& b : xunpack->boxes)
+                if (peer_buf[size_t(b.buf_slot)]) boxes.push_back(b);
+        if (!boxes.empty()) xpack = std::make_unique<xplan>(std::move(boxes));
+    }
+    cs_self_form = n_self == entries[0].size() && !any_peer ? 1 : 2;
+    cs_self_accum = std::move(accum);
+    cs_self_pack = std::move(pack);
+    cs_self_xpack = std::move(xpack);
 }
 
 int exchange_plan::execute_buffer(int dir, int b, void* const* fptr, int nf, void* const* bptr,

@@ -7,6 +7,7 @@
 #include <memory>
 #include <vector>
 
+#include "ghx_pattern.hpp"
 #include "ghx_plan.hpp"
 
 namespace ghx
@@ -113,6 +114,18 @@ struct exchange_plan
     std::unique_ptr<splan> cs_adj_pack;  // null: no ordinary receive segment
     std::unique_ptr<::ghx_saccum> cs_adj_accum;  // the handle type: ghx_cs_exchange_adjoint_plan lends it
     void make_cs_adjoint(const int32_t* dtypes, int32_t n);
+    // the same adjoint with the self messages fused (ghx_cs_exchange_adjoint_self_create, DESIGN.md
+    // §4.8): the get plan (k_accum_get_x) reads a self message from the receiving field's halo cells
+    // through the edge's transform, and the reverse pack covers the peer receive spaces alone: the
+    // kept ordinary segments and xunpack's boxes filtered by receive buffer (both null: every
+    // message is a self message). cs_rhalos: a copy of the halo entry (boxes in both coordinates,
+    // tiles) behind each of entries[1], kept by make_exchange. form: 0 none, 1 all self, 2 mixed.
+    std::vector<halo_entry> cs_rhalos;
+    int32_t cs_self_form = 0;
+    std::unique_ptr<splan> cs_self_pack;
+    std::unique_ptr<xplan> cs_self_xpack;
+    std::unique_ptr<::ghx_saccum> cs_self_accum;
+    void make_cs_adjoint_self(const int32_t* dtypes, int32_t n);
 
     void make_split();  // the per-buffer plans (ghx_exchange_split)
 

@@ -389,10 +389,17 @@ struct alignas(16) sacc_src
     uint64_t stride[4];   // buffer byte stride of outer dim k of the sub-box in this box
     uint32_t buf_slot;    // index in the launch's source pointer table (kargs_sa::buf_ptr)
     uint32_t flags;       // bit 0: a field source (k_accum_get_s: a receiving field's halo cells,
-                          // zeroed after the load when the launch has zero_halos); else 0
+                          // zeroed after the load when the launch has zero_halos); bits 1-2: the
+                          // vector components 0 / 1 this source negates (k_accum_get_x: a halo read
+                          // across a cube edge, strides signed mod 2^64); else 0
 };
 static_assert(sizeof(sacc_src) == 48, "sacc_src layout");
 constexpr uint32_t kSaccFieldSrc = 1u;
+constexpr uint32_t kSaccNegShift = 1;
+// sacc_tile::comp: where the component index of a lane's vector comes from
+constexpr uint8_t kSaccCompNone = 0;  // no source of the sub-box negates some components and not others
+constexpr uint8_t kSaccCompRow = 5;   // the row is one vector of the field: byte column / element size
+                                      // (1..4: outer coordinate c[comp - 1])
 // Tile record, one per workgroup tile: the sub-box with the tile's part of it — n_rows rows from
 // first_row on, of each the `len` bytes from byte col0 on (col0 > 0 only where one row is longer
 // than a tile: then n_rows = 1 and col0 a multiple of 16). A lane takes one vector of the tile's
@@ -417,7 +424,9 @@ struct alignas(16) sacc_tile
     uint8_t wlog2;        // log2 of the widest vector (<= 16 B) dividing the row, the field offset
                           // and strides and every source's buffer offset and strides
     uint8_t n_outer;
-    uint8_t pad[2];
+    uint8_t comp;         // k_accum_get_x: kSaccComp*, which tile axis carries the components a
+                          // source's mask (sacc_src::flags) speaks of; 0 in every other plan
+    uint8_t pad;
 };
 static_assert(sizeof(sacc_tile) == 128, "sacc_tile layout");
 struct kargs_sa
@@ -481,6 +490,7 @@ int launch_pack_self_u(const kargs_um& a, void* stream, uint32_t grid, bool runs
 int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid);
 int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid);
 int launch_accum_get_s(const kargs_sa& a, void* stream, uint32_t grid);  // k_accum_get_s
+int launch_accum_get_x(const kargs_sa& a, void* stream, uint32_t grid);  // k_accum_get_x
 uint32_t grid_for_tiles(uint32_t n_tiles);
 void timing_enable(bool on);                            // ghx_launch_timing
 int timing_read(float* ms, int32_t cap, int32_t* n);    // ghx_launch_timing_read

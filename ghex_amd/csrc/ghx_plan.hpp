@@ -345,8 +345,23 @@ struct saccum_plan
     bool get = false;
     std::vector<int32_t> tab_slot;
     uint32_t tab_field = 0, n_field_sources = 0;
+    // A cubed-sphere get plan (ghx_cs_exchange_adjoint_self_create, k_accum_get_x): `space` gives per
+    // contribution entry with a source the receiving side of each of its boxes as cs_space_box
+    // describes it (axes of the dense box in layout order). A paired box then reads the halo cell
+    // its cell is the image of: origin and signed strides from the space, and the components the
+    // edge negates in the source record's flags. n_rotated_sources: the paired boxes whose source
+    // is not addressed as the receiving field's own box would be (transposed, reversed or signed).
+    bool rotated = false;
+    uint32_t n_rotated_sources = 0;
+    struct source_map  // per source record, for inspection: its signed byte stride per dimension of
+    {                  // the contribution's field, the components it negates, the component dimension
+        int64_t stride[GHX_MAX_DIM];
+        uint8_t neg;
+        int8_t comp_dim;
+    };
+    std::vector<source_map> src_map;
     saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, int n, const ghx_pack_entry* zero,
-                int n_zero, const ghx_pack_entry* const* source = nullptr);
+                int n_zero, const ghx_pack_entry* const* source = nullptr, const xseg* const* space = nullptr);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
     int execute_get(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
 };

@@ -66,8 +66,10 @@ struct cbox
     uint64_t buf_off;
     uint64_t bstride[GHX_MAX_DIM];
     // a field source (get plan): buf_slot is the source field's slot, buf_off the field byte offset
-    // of the source box's origin and bstride the source field's byte strides
+    // of the source box's origin and bstride the source field's byte strides (a cubed-sphere space:
+    // of the image of the box's first cell, and signed strides mod 2^64; neg: the components it negates)
     bool field_src;
+    uint8_t neg;
 };
 
 struct slot_boxes
@@ -106,8 +108,8 @@ saccum_plan::tables::~tables()
 }
 
 saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, int n, const ghx_pack_entry* zero,
-                         int n_zero, const ghx_pack_entry* const* source)
-    : get(source != nullptr)
+                         int n_zero, const ghx_pack_entry* const* source, const xseg* const* space)
+    : get(source != nullptr), rotated(source != nullptr && space != nullptr)
 {
     std::map<int32_t, slot_boxes> slots;
     enum { k_sum, k_zero, k_src };
@@ -175,7 +177,7 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         }
     };
     // contribution entry e reads box k of `src` where it would read box k of its buffer
-    auto pair_entry = [&](const ghx_pack_entry& en, uint32_t e, const ghx_pack_entry& src) {
+    auto pair_entry = [&](const ghx_pack_entry& en, uint32_t e, const ghx_pack_entry& src, const xseg* sp) {
         const ghx_field_desc &f = en.field, &g = src.field;
         const std::string who = "contribution entry " + std::to_string(e) + " and its source ";
         validate_field(g);
@@ -187,7 +189,7 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         for (int d = 0; d < f.dim; ++d)
             if (f.layout[d] != g.layout[d]) throw invalid(who + "differ in layout order");
         const int spatial = f.dim - (f.has_components ? 1 : 0);
-        for (int b = 0; b < en.n_boxes; ++b)
+        for (int b = 0; !sp && b < en.n_boxes; ++b)
             for (int d = 0; d < spatial; ++d)
                 if (int64_t(en.boxes[b].last[d]) - en.boxes[b].first[d] != int64_t(src.boxes[b].last[d]) - src.boxes[b].first[d])
                     throw invalid(who + "differ in the extents of box " + std::to_string(b));
@@ -203,6 +205,42 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
             c.buf_slot = q.buf_slot;
             c.buf_off = q.buf_off;
             for (int d = 0; d < f.dim; ++d) c.bstride[d] = q.bstride[d];
+            if (!sp) continue;
+            // a cubed-sphere space: axis a of its dense box is the sender's dim by_speed[a]. The map
+            // cell -> halo cell must be a bijection of the box onto the source box q: every axis
+            // runs along one dim of q of the same extent, and the first cell's image is q's corner
+            // at the first or, along a reversed axis, the last coordinate
+            const xseg& x = sp[b];
+            const int D = f.dim;
+            int by_speed[GHX_MAX_DIM];
+            for (int d = 0; d < D; ++d) by_speed[D - 1 - f.layout[d]] = d;
+            const std::string shape = who + "differ in shape under the tile transform (box " + std::to_string(b) + ")";
+            bool used[GHX_MAX_DIM] = {};
+            int64_t origin = 0;
+            bool moved = x.neg_mask != 0;
+            for (int a = 0; a < D; ++a)
+            {
+                const int d = by_speed[a];
+                const int64_t ext = c.last[d] - c.first[d] + 1;
+                if (int64_t(x.ext[a]) != ext) throw invalid(shape);
+                int to = -1;
+                for (int r = 0; r < D && to < 0; ++r)
+                    if (!used[r] && q.last[r] - q.first[r] + 1 == ext &&
+                        (x.stride[a] == g.byte_strides[r] || x.stride[a] == -g.byte_strides[r]))
+                        to = r;
+                if (to < 0) throw invalid(shape);
+                used[to] = true;
+                const bool up = x.stride[a] == g.byte_strides[to];
+                origin += ((up ? q.first[to] : q.last[to]) + (to < spatial ? g.offsets[to] : 0)) * g.byte_strides[to];
+                c.bstride[d] = uint64_t(x.stride[a]);
+                moved = moved || to != d || !up;
+            }
+            if (origin != x.field_off)
+                throw invalid(who + "differ in shape under the tile transform (the image of box " + std::to_string(b) +
+                              " is not its source box)");
+            c.buf_off = uint64_t(x.field_off);
+            c.neg = x.neg_mask;
+            if (moved) ++n_rotated_sources;
         }
     };
     for (int e = 0; e < n; ++e)
@@ -221,7 +259,7 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         dt = dtypes[e];
         if (src)
         {
-            pair_entry(en, uint32_t(e), *src);
+            pair_entry(en, uint32_t(e), *src, space ? space[e] : nullptr);
             ++n_field_sources;
             continue;
         }
@@ -322,6 +360,12 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         const int cont = by_speed[0];
         bool unit = f.byte_strides[cont] == elem;
         for (uint32_t j : list) unit = unit && from[j].bstride[cont] == uint64_t(elem);  // a strided source field
+        // a source that negates some components of a vector and not the others: the component
+        // dimension stays a tile axis of its own, and where it is the row the lanes take elements
+        const int comp = f.has_components ? D - 1 : -1;
+        bool mixed = false;
+        for (uint32_t j : list) mixed = mixed || (from[j].neg && f.num_components > 1);
+        const bool comp_row = mixed && unit && cont == comp;
         int64_t L = unit ? ext[cont] * elem : elem;
         int outer[GHX_MAX_DIM];
         int n_outer = 0;
@@ -330,6 +374,7 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         // rows that are adjacent in the field and in every source's buffer box are one row
         auto mergeable = [&] {
             if (n_outer == 0 || f.byte_strides[outer[0]] != L || L * ext[outer[0]] >= (int64_t(1) << 30)) return false;
+            if (mixed && (comp_row || outer[0] == comp)) return false;
             for (uint32_t j : list)
                 if (from[j].bstride[outer[0]] != uint64_t(L)) return false;
             return true;
@@ -344,6 +389,10 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
         sacc_tile t{};
         uint64_t rows = 1;
         int w = wlog2_of(uint64_t(L));
+        if (comp_row) w = std::min(w, wlog2_of(uint64_t(elem)));
+        t.comp = comp_row ? kSaccCompRow : kSaccCompNone;
+        for (int k = 0; mixed && !comp_row && k < n_outer; ++k)
+            if (outer[k] == comp) t.comp = uint8_t(1 + k);
         for (int d = 0; d < D; ++d) t.field_off += (lo[d] + (d < spatial ? f.offsets[d] : 0)) * f.byte_strides[d];
         w = std::min(w, wlog2_of(uint64_t(t.field_off)));
         for (int k = 0; k < 4; ++k)
@@ -361,7 +410,7 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
             s.buf_off = c.buf_off;
             for (int d = 0; d < spatial; ++d) s.buf_off += uint64_t(lo[d] - c.first[d]) * c.bstride[d];
             s.buf_slot = uint32_t(c.field_src ? tab_of_field[c.buf_slot] : tab_of_buf[c.buf_slot]);
-            s.flags = c.field_src ? kSaccFieldSrc : 0;
+            s.flags = (c.field_src ? kSaccFieldSrc : 0) | (uint32_t(c.neg) << kSaccNegShift);
             w = std::min(w, wlog2_of(s.buf_off));
             for (int k = 0; k < n_outer; ++k)
             {
@@ -370,6 +419,11 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
             }
             t.buf_mask |= uint64_t(1) << s.buf_slot;
             srcs.push_back(s);
+            source_map m{};
+            for (int d = 0; d < D; ++d) m.stride[d] = int64_t(c.bstride[d]);
+            m.neg = c.neg;
+            m.comp_dim = int8_t(comp);
+            src_map.push_back(m);
             src_entry.push_back(c.entry);
             src_box.push_back(c.box);
         }
@@ -531,7 +585,8 @@ int saccum_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, b
     return launch_accum_s(a, stream, grid_for_tiles(n_tiles));
 }
 
-// k_accum_get_s: the source pointer table holds the buffers that are read, then the source fields
+// k_accum_get_s (k_accum_get_x: a plan with cubed-sphere spaces): the source pointer table holds the
+// buffers that are read, then the source fields
 int saccum_plan::execute_get(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const
 {
     if (!get) throw invalid("not a get plan (ghx_saccum_get_create)");
@@ -565,7 +620,8 @@ int saccum_plan::execute_get(void* const* fptr, int nf, void* const* bptr, int n
     if (!dev.tiles) throw hip_error("plan has no device tables (no HIP device at creation)");
     a.tiles = static_cast<const sacc_tile*>(dev.tiles);
     a.srcs = static_cast<const sacc_src*>(dev.srcs);
-    return launch_accum_get_s(a, stream, grid_for_tiles(n_tiles));
+    return rotated ? launch_accum_get_x(a, stream, grid_for_tiles(n_tiles))
+                   : launch_accum_get_s(a, stream, grid_for_tiles(n_tiles));
 }
 
 }  // namespace ghx

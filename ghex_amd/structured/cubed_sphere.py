@@ -21,14 +21,18 @@ from .regular import _layout_order
 
 
 def make_communication_object(context, fuse_rotated: bool = False, adjoint_rotated: bool = False,
-                              **options) -> CommunicationObject:
+                              fuse_adjoint_rotated: bool = False, **options) -> CommunicationObject:
     """The plain communication object. fuse_rotated=True (opt-in): an exchange whose every
     message stays on this rank (a whole cube on one rank) runs as ONE launch that packs and
     rotates (ghx_cs_exchange_self); any other exchange takes the usual three launches.
     adjoint_rotated=True (opt-in): adjoint_exchange and its siblings take cubed-sphere fields
-    (ghx_cs_exchange_adjoint_*: a reverse pack that rotates and negates, then the accumulate)."""
+    (ghx_cs_exchange_adjoint_*: a reverse pack that rotates and negates, then the accumulate).
+    fuse_adjoint_rotated=True (opt-in, with adjoint_rotated): the adjoint adds the halo cells of
+    self messages straight into their owner cells, through the edge's transform, in the accumulate
+    launch (ghx_cs_exchange_adjoint_self_*, k_accum_get_x); their buffers are not touched. A whole
+    cube on one rank then runs its adjoint as ONE launch."""
     return CommunicationObject(context, fuse_rotated=fuse_rotated, adjoint_rotated=adjoint_rotated,
-                               **options)
+                               fuse_adjoint_rotated=fuse_adjoint_rotated, **options)
 
 
 def make_bulk_communication_object(context, epochs: str = "device", timeout: float = 30.0,

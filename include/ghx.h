@@ -1159,6 +1159,55 @@ int ghx_cs_exchange_adjoint_accumulate(const ghx_exchange* ex, void* const* fiel
                                        int32_t n_fields, void* const* send_buffers, int32_t n_send,
                                        int32_t zero_halos, ghx_stream stream);
 
+/* The cubed-sphere adjoint with the self messages fused (k_accum_get_x), the twin of
+ * ghx_sexchange_adjoint_self_*. A message whose receiver is a field of this rank is accumulated
+ * straight from that field's halo cells: for every send entry, box and cell, in ascending (send
+ * entry, box), S[cell] += s_k * R[T^-1(cell)] in the element type, R the receiving field of the same
+ * message, T the edge's transform, s_k = -1 for the components it negates (a sign-bit flip for
+ * floats, two's complement for integers, applied to the loaded value before the add: the bits are
+ * those of ghx_cs_exchange_adjoint_pack + _accumulate). With zero_halos the lane that loaded a halo
+ * value stores zero bytes over it. The buffers of self messages are neither written nor read, and
+ * no buffer slot is spent on them: a whole 24-domain cube on one rank has an adjoint here with up
+ * to two fields per domain (at most 64 field slots and 64 source-table slots, one launch).
+ * self_create attaches the get plan — every send entry of a self message sourced by the receive
+ * entry at the same message bytes, box k by box k, each box addressed through its space's transform
+ * — and, where peer messages remain, the reverse pack of the peer receive spaces alone (the kept
+ * ordinary segments and the transformed boxes, filtered by receive buffer). It refuses what
+ * ghx_cs_exchange_adjoint_create refuses except that call's buffer-slot count, an exchange with no
+ * self message, a self message whose two sides do not pair (element size, components, layout
+ * order, number of boxes, shape under the transform), and ghx_saccum_get_create's reasons; it
+ * leaves the plans of ghx_cs_exchange_adjoint_create alone. self_info works on any exchange and
+ * without a device: form 0 = none, 1 = every message is a self message, 2 = mixed; sum sub-boxes,
+ * source records, the contribution entries with a field source, and the paired boxes whose source
+ * is transposed, reversed or signed. self_plan lends the plan (owned by the exchange) to
+ * ghx_saccum_info / _box / _source / _source_kind / _source_map. self_segments: the ordinary
+ * segments and the k_pack_x records (spaces) of form 2's reverse pack (0 in form 1 and before
+ * create). ghx_saccum_source_map (host only, any plan): source record j's signed byte stride per
+ * dimension of the contribution's field (strides[GHX_MAX_DIM]; a buffer source: its dense box's),
+ * the components it negates (bit k: component k) and the component dimension (-1: none); with
+ * ghx_saccum_source_kind's origin, cell (i_d) of a sub-box reads origin + sum (i_d - first_d) *
+ * strides[d]. self_pack has ghx_cs_exchange_adjoint_pack's argument contract: form 1 launches
+ * nothing, form 2 gathers the peer messages' halo cells. self_accumulate has
+ * ghx_cs_exchange_adjoint_accumulate's: one k_accum_get_x launch, self messages from the halos,
+ * peer messages from the send buffers; receive entries of peer messages get zero tiles. Both fail
+ * with GHX_ERR_INVALID before self_create and while a direction has parity set, allocate nothing
+ * and can be captured in a graph. */
+int ghx_cs_exchange_adjoint_self_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items);
+int ghx_cs_exchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64_t* n_boxes,
+                                      int64_t* n_sources, int64_t* n_field_sources,
+                                      int64_t* n_rotated_sources);
+int ghx_cs_exchange_adjoint_self_plan(const ghx_exchange* ex, const ghx_saccum** out);
+int ghx_cs_exchange_adjoint_self_segments(const ghx_exchange* ex, int32_t* n_pack_segments,
+                                          int32_t* n_pack_x_records);
+int ghx_saccum_source_map(const ghx_saccum* p, int64_t j, int64_t* strides, int32_t* neg_mask,
+                          int32_t* comp_dim);
+int ghx_cs_exchange_adjoint_self_pack(const ghx_exchange* ex, void* const* field_ptrs,
+                                      int32_t n_fields, void* const* recv_buffers, int32_t n_recv,
+                                      ghx_stream stream);
+int ghx_cs_exchange_adjoint_self_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
+                                            int32_t n_fields, void* const* send_buffers,
+                                            int32_t n_send, int32_t zero_halos, ghx_stream stream);
+
 /* Device-side access epochs of the zero-copy exchanges (bulk puts, direct pack): the reference's
  * access guards (include/ghex/rma/access_guard.hpp:35-140; per range: start/end_target_epoch on
  * the owner, start/end_source_epoch on the putter; include/ghex/bulk_communication_object.hpp
