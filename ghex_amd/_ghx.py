@@ -166,10 +166,7 @@ _SIGS = {
     "ghx_uaccum_dest": (c_i32, [c_vp, c_i64, P(UAccumDestInfo)]),
     "ghx_uaccum_contrib": (c_i32, [c_vp, c_i64, P(c_i32), P(c_i64)]),
     "ghx_uaccum_destroy": (c_i32, [c_vp]),
-    "ghx_uexchange_adjoint_create": (c_i32, [c_vp, P(c_i32), c_i32]),
     "ghx_uexchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64)]),
-    "ghx_uexchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
-    "ghx_uexchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_saccum_create": (c_i32, [P(PackEntry), P(c_i32), c_i32, P(PackEntry), c_i32, P(c_vp)]),
     "ghx_saccum_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_saccum_info": (c_i32, [c_vp, P(c_u64), P(c_i64), P(c_i64), P(c_i64), P(c_i64), P(c_i32)]),
@@ -179,27 +176,15 @@ _SIGS = {
     "ghx_saccum_get_create": (c_i32, [P(PackEntry), P(c_i32), P(P(PackEntry)), c_i32, P(PackEntry), c_i32, P(c_vp)]),
     "ghx_saccum_get_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_saccum_source_kind": (c_i32, [c_vp, c_i64, P(c_i32), P(c_i32), P(c_u64)]),
-    "ghx_sexchange_adjoint_self_create": (c_i32, [c_vp, P(c_i32), c_i32]),
     "ghx_sexchange_adjoint_self_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i64)]),
-    "ghx_sexchange_adjoint_self_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
-    "ghx_sexchange_adjoint_self_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
-    "ghx_sexchange_adjoint_create": (c_i32, [c_vp, P(c_i32), c_i32]),
     "ghx_sexchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64)]),
-    "ghx_sexchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
-    "ghx_sexchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
-    "ghx_cs_exchange_adjoint_create": (c_i32, [c_vp, P(c_i32), c_i32]),
     "ghx_cs_exchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i32), P(c_i32)]),
     "ghx_cs_exchange_adjoint_plan": (c_i32, [c_vp, P(c_vp)]),
     "ghx_cs_exchange_adjoint_segments": (c_i32, [c_vp, P(c_i32), P(c_i32)]),
-    "ghx_cs_exchange_adjoint_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
-    "ghx_cs_exchange_adjoint_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
-    "ghx_cs_exchange_adjoint_self_create": (c_i32, [c_vp, P(c_i32), c_i32]),
     "ghx_cs_exchange_adjoint_self_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i64), P(c_i64)]),
     "ghx_cs_exchange_adjoint_self_plan": (c_i32, [c_vp, P(c_vp)]),
     "ghx_cs_exchange_adjoint_self_segments": (c_i32, [c_vp, P(c_i32), P(c_i32)]),
     "ghx_saccum_source_map": (c_i32, [c_vp, c_i64, P(c_i64), P(c_i32), P(c_i32)]),
-    "ghx_cs_exchange_adjoint_self_pack": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp]),
-    "ghx_cs_exchange_adjoint_self_accumulate": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_cs_unpack": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
                               c_i32, c_vp]),
     "ghx_cs_pack_rotated": (c_i32, [P(FieldDesc), P(CsItem), c_vp, c_vp, P(Box), P(Box), P(c_i32),
@@ -282,6 +267,12 @@ _SIGS = {
     "ghx_copier_acquire": (c_i32, [c_vp, c_vp]),
     "ghx_copier_destroy": (c_i32, [c_vp]),
 }
+# the five adjoint families' create, reverse pack and accumulate take the same arguments
+for _prefix in ("ghx_uexchange_adjoint", "ghx_sexchange_adjoint", "ghx_sexchange_adjoint_self",
+                "ghx_cs_exchange_adjoint", "ghx_cs_exchange_adjoint_self"):
+    _SIGS[_prefix + "_create"] = (c_i32, [c_vp, P(c_i32), c_i32])
+    _SIGS[_prefix + "_pack"] = (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp])
+    _SIGS[_prefix + "_accumulate"] = (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp])
 EXPORTED = tuple(_SIGS)
 
 _lib = None

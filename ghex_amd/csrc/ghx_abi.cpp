@@ -1291,13 +1291,79 @@ int ghx_uaccum_destroy(ghx_uaccum* p)
     });
 }
 
-int ghx_uexchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
+// The adjoint of an exchange: five kinds of plan set (exchange_plan::adjoint_kind), one create, one
+// reverse pack and one accumulate behind the entry points of each.
+namespace
+{
+using adjoint_kind = exchange_plan::adjoint_kind;
+using adjoint_set = exchange_plan::adjoint_set;
+
+// per kind: what a launch or a *_plan call says of a set that was not created
+const char* const k_no_adjoint[exchange_plan::n_adjoint_kinds] = {
+    "adjoint exchange: no adjoint plans (ghx_uexchange_adjoint_create)",
+    "adjoint exchange: no adjoint plans (ghx_sexchange_adjoint_create)",
+    "fused adjoint exchange: no plans (ghx_sexchange_adjoint_self_create)",
+    "cubed-sphere adjoint exchange: no adjoint plans (ghx_cs_exchange_adjoint_create)",
+    "fused cubed-sphere adjoint exchange: no plans (ghx_cs_exchange_adjoint_self_create)"};
+
+const adjoint_set* created_adjoint(const ghx_exchange* ex, adjoint_kind kind)
+{
+    check_ptr(ex, "exchange");
+    if (!ex->adjoint[kind].form) throw invalid(k_no_adjoint[kind]);
+    return &ex->adjoint[kind];
+}
+
+// a launch: both launches of the adjoint use one copy of each buffer
+const adjoint_set* check_adjoint(const ghx_exchange* ex, adjoint_kind kind)
+{
+    const adjoint_set* set = created_adjoint(ex, kind);
+    ex->check_single_buffered();
+    return set;
+}
+
+int adjoint_create(ghx_exchange* ex, adjoint_kind kind, const int32_t* dtypes, int32_t n_items)
 {
     return guarded([&] {
         check_ptr(ex, "exchange");
-        ex->make_adjoint(dtypes, n_items);
+        ex->make_adjoint(kind, dtypes, n_items);
         return GHX_OK;
     });
+}
+
+int adjoint_pack(const ghx_exchange* ex, adjoint_kind kind, void* const* field_ptrs, int32_t n_fields,
+                 void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
+{
+    return guarded([&] {
+        const adjoint_set* set = check_adjoint(ex, kind);
+        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
+        return set->pack(field_ptrs, n_fields, recv_buffers, n_recv, stream);
+    });
+}
+
+int adjoint_accumulate(const ghx_exchange* ex, adjoint_kind kind, void* const* field_ptrs, int32_t n_fields,
+                       void* const* send_buffers, int32_t n_send, int32_t zero_halos, ghx_stream stream)
+{
+    return guarded([&] {
+        const adjoint_set* set = check_adjoint(ex, kind);
+        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
+        return set->accumulate(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
+    });
+}
+
+// the *_info calls' counts of a structured accumulate plan (null: not created, every count 0)
+void saccum_counts(const saccum_plan* p, int64_t* n_boxes, int64_t* n_sources, int64_t* n_field_sources,
+                   int64_t* n_rotated_sources)
+{
+    if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
+    if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
+    if (n_field_sources) *n_field_sources = p ? int64_t(p->n_field_sources) : 0;
+    if (n_rotated_sources) *n_rotated_sources = p ? int64_t(p->n_rotated_sources) : 0;
+}
+}  // namespace
+
+int ghx_uexchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
+{
+    return adjoint_create(ex, exchange_plan::adj_list, dtypes, n_items);
 }
 
 int ghx_uexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_dest,
@@ -1306,7 +1372,7 @@ int ghx_uexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* 
     return guarded([&] {
         check_ptr(ex, "exchange");
         check_ptr(ready, "ready");
-        const uaccum_plan* p = ex->adj_accum.get();
+        const uaccum_plan* p = ex->adjoint[exchange_plan::adj_list].uaccum.get();
         *ready = p ? 1 : 0;
         if (n_dest) *n_dest = p ? int64_t(p->n_dest) : 0;
         if (n_contrib) *n_contrib = p ? int64_t(p->contribs.size()) : 0;
@@ -1314,39 +1380,18 @@ int ghx_uexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* 
     });
 }
 
-namespace
-{
-// both launches of the adjoint use one copy of each buffer
-void check_adjoint(const ghx_exchange* ex)
-{
-    check_ptr(ex, "exchange");
-    if (!ex->adj_accum || !ex->adj_pack)
-        throw invalid("adjoint exchange: no adjoint plans (ghx_uexchange_adjoint_create)");
-    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-}
-}  // namespace
-
 int ghx_uexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
 {
-    return guarded([&] {
-        check_adjoint(ex);
-        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
-        return ex->adj_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
-    });
+    return adjoint_pack(ex, exchange_plan::adj_list, field_ptrs, n_fields, recv_buffers, n_recv, stream);
 }
 
 int ghx_uexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
                                      int32_t n_fields, void* const* send_buffers, int32_t n_send,
                                      int32_t zero_halos, ghx_stream stream)
 {
-    return guarded([&] {
-        check_adjoint(ex);
-        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
-        return ex->adj_accum->execute(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
-    });
+    return adjoint_accumulate(ex, exchange_plan::adj_list, field_ptrs, n_fields, send_buffers, n_send, zero_halos,
+                              stream);
 }
 
 int ghx_saccum_create(const ghx_pack_entry* contrib, const int32_t* dtypes, int32_t n,
@@ -1470,11 +1515,7 @@ int ghx_saccum_destroy(ghx_saccum* p)
 
 int ghx_sexchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
 {
-    return guarded([&] {
-        check_ptr(ex, "exchange");
-        ex->make_sadjoint(dtypes, n_items);
-        return GHX_OK;
-    });
+    return adjoint_create(ex, exchange_plan::adj_boxes, dtypes, n_items);
 }
 
 int ghx_sexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_boxes, int64_t* n_sources)
@@ -1482,55 +1523,30 @@ int ghx_sexchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* 
     return guarded([&] {
         check_ptr(ex, "exchange");
         check_ptr(ready, "ready");
-        const saccum_plan* p = ex->sadj_accum.get();
-        *ready = p ? 1 : 0;
-        if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
-        if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
+        const adjoint_set& set = ex->adjoint[exchange_plan::adj_boxes];
+        *ready = set.form ? 1 : 0;
+        saccum_counts(set.saccum.get(), n_boxes, n_sources, nullptr, nullptr);
         return GHX_OK;
     });
 }
 
-namespace
-{
-void check_sadjoint(const ghx_exchange* ex)
-{
-    check_ptr(ex, "exchange");
-    if (!ex->sadj_accum || !ex->sadj_pack)
-        throw invalid("adjoint exchange: no adjoint plans (ghx_sexchange_adjoint_create)");
-    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-}
-}  // namespace
-
 int ghx_sexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
 {
-    return guarded([&] {
-        check_sadjoint(ex);
-        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
-        return ex->sadj_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
-    });
+    return adjoint_pack(ex, exchange_plan::adj_boxes, field_ptrs, n_fields, recv_buffers, n_recv, stream);
 }
 
 int ghx_sexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
                                      int32_t n_fields, void* const* send_buffers, int32_t n_send,
                                      int32_t zero_halos, ghx_stream stream)
 {
-    return guarded([&] {
-        check_sadjoint(ex);
-        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
-        return ex->sadj_accum->execute(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
-    });
+    return adjoint_accumulate(ex, exchange_plan::adj_boxes, field_ptrs, n_fields, send_buffers, n_send, zero_halos,
+                              stream);
 }
 
 int ghx_sexchange_adjoint_self_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
 {
-    return guarded([&] {
-        check_ptr(ex, "exchange");
-        ex->make_sadjoint_self(dtypes, n_items);
-        return GHX_OK;
-    });
+    return adjoint_create(ex, exchange_plan::adj_boxes_self, dtypes, n_items);
 }
 
 int ghx_sexchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64_t* n_boxes, int64_t* n_sources,
@@ -1539,57 +1555,30 @@ int ghx_sexchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64
     return guarded([&] {
         check_ptr(ex, "exchange");
         check_ptr(form, "form");
-        const saccum_plan* p = ex->sself_accum.get();
-        *form = p ? ex->sself_form : 0;
-        if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
-        if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
-        if (n_field_sources) *n_field_sources = p ? int64_t(p->n_field_sources) : 0;
+        const adjoint_set& set = ex->adjoint[exchange_plan::adj_boxes_self];
+        *form = set.form;
+        saccum_counts(set.saccum.get(), n_boxes, n_sources, n_field_sources, nullptr);
         return GHX_OK;
     });
 }
 
-namespace
-{
-void check_sadjoint_self(const ghx_exchange* ex)
-{
-    check_ptr(ex, "exchange");
-    if (!ex->sself_accum)
-        throw invalid("fused adjoint exchange: no plans (ghx_sexchange_adjoint_self_create)");
-    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-}
-}  // namespace
-
 int ghx_sexchange_adjoint_self_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                     void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
 {
-    return guarded([&] {
-        check_sadjoint_self(ex);
-        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
-        if (!ex->sself_pack) return int(GHX_OK);  // every message is a self message: nothing to gather
-        return ex->sself_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
-    });
+    return adjoint_pack(ex, exchange_plan::adj_boxes_self, field_ptrs, n_fields, recv_buffers, n_recv, stream);
 }
 
 int ghx_sexchange_adjoint_self_accumulate(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                           void* const* send_buffers, int32_t n_send, int32_t zero_halos,
                                           ghx_stream stream)
 {
-    return guarded([&] {
-        check_sadjoint_self(ex);
-        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
-        return ex->sself_accum->execute_get(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
-    });
+    return adjoint_accumulate(ex, exchange_plan::adj_boxes_self, field_ptrs, n_fields, send_buffers, n_send,
+                              zero_halos, stream);
 }
 
 int ghx_cs_exchange_adjoint_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
 {
-    return guarded([&] {
-        check_ptr(ex, "exchange");
-        ex->make_cs_adjoint(dtypes, n_items);
-        return GHX_OK;
-    });
+    return adjoint_create(ex, exchange_plan::adj_cs, dtypes, n_items);
 }
 
 int ghx_cs_exchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t* n_boxes, int64_t* n_sources,
@@ -1598,37 +1587,21 @@ int ghx_cs_exchange_adjoint_info(const ghx_exchange* ex, int32_t* ready, int64_t
     return guarded([&] {
         check_ptr(ex, "exchange");
         check_ptr(ready, "ready");
-        const saccum_plan* p = ex->cs_adj_ready ? ex->cs_adj_accum.get() : nullptr;
-        *ready = p ? 1 : 0;
-        if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
-        if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
-        if (n_pack_x_records) *n_pack_x_records = p && ex->xunpack ? ex->xunpack->n_records : 0;
-        if (n_pack_x_tiles) *n_pack_x_tiles = p && ex->xunpack ? int32_t(ex->xunpack->n_tiles) : 0;
+        const adjoint_set& set = ex->adjoint[exchange_plan::adj_cs];
+        *ready = set.form ? 1 : 0;
+        saccum_counts(set.saccum.get(), n_boxes, n_sources, nullptr, nullptr);
+        if (n_pack_x_records) *n_pack_x_records = set.xpack ? set.xpack->n_records : 0;
+        if (n_pack_x_tiles) *n_pack_x_tiles = set.xpack ? int32_t(set.xpack->n_tiles) : 0;
         return GHX_OK;
     });
 }
-
-namespace
-{
-void check_cs_adjoint(const ghx_exchange* ex)
-{
-    check_ptr(ex, "exchange");
-    if (!ex->cs_adj_ready)
-        throw invalid("cubed-sphere adjoint exchange: no adjoint plans (ghx_cs_exchange_adjoint_create)");
-    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-}
-}  // namespace
 
 int ghx_cs_exchange_adjoint_plan(const ghx_exchange* ex, const ghx_saccum** out)
 {
     return guarded([&] {
         check_ptr(ex, "exchange");
         check_ptr(out, "out");
-        if (!ex->cs_adj_ready)
-            throw invalid("cubed-sphere adjoint exchange: no adjoint plans (ghx_cs_exchange_adjoint_create)");
-        *out = ex->cs_adj_accum.get();
+        *out = created_adjoint(ex, exchange_plan::adj_cs)->saccum.get();
         return GHX_OK;
     });
 }
@@ -1637,7 +1610,8 @@ int ghx_cs_exchange_adjoint_segments(const ghx_exchange* ex, int32_t* n_pack_seg
 {
     return guarded([&] {
         check_ptr(ex, "exchange");
-        if (n_pack_segments) *n_pack_segments = ex->cs_adj_pack ? ex->cs_adj_pack->n_segments : 0;
+        const adjoint_set& set = ex->adjoint[exchange_plan::adj_cs];
+        if (n_pack_segments) *n_pack_segments = set.spack ? set.spack->n_segments : 0;
         if (n_unpack_segments) *n_unpack_segments = ex->cubed_sphere && ex->sunpack ? ex->sunpack->n_segments : 0;
         return GHX_OK;
     });
@@ -1646,36 +1620,20 @@ int ghx_cs_exchange_adjoint_segments(const ghx_exchange* ex, int32_t* n_pack_seg
 int ghx_cs_exchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                  void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
 {
-    return guarded([&] {
-        check_cs_adjoint(ex);
-        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
-        int rc = GHX_OK;
-        if (ex->cs_adj_pack) rc = ex->cs_adj_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
-        // the transformed spaces, after the ordinary launch on the same stream
-        if (rc == GHX_OK && ex->xunpack)
-            rc = ex->xunpack->execute_pack(field_ptrs, n_fields, recv_buffers, n_recv, stream);
-        return rc;
-    });
+    return adjoint_pack(ex, exchange_plan::adj_cs, field_ptrs, n_fields, recv_buffers, n_recv, stream);
 }
 
 int ghx_cs_exchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                        void* const* send_buffers, int32_t n_send, int32_t zero_halos,
                                        ghx_stream stream)
 {
-    return guarded([&] {
-        check_cs_adjoint(ex);
-        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
-        return ex->cs_adj_accum->execute(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
-    });
+    return adjoint_accumulate(ex, exchange_plan::adj_cs, field_ptrs, n_fields, send_buffers, n_send, zero_halos,
+                              stream);
 }
 
 int ghx_cs_exchange_adjoint_self_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
 {
-    return guarded([&] {
-        check_ptr(ex, "exchange");
-        ex->make_cs_adjoint_self(dtypes, n_items);
-        return GHX_OK;
-    });
+    return adjoint_create(ex, exchange_plan::adj_cs_self, dtypes, n_items);
 }
 
 int ghx_cs_exchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64_t* n_boxes, int64_t* n_sources,
@@ -1684,37 +1642,19 @@ int ghx_cs_exchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int
     return guarded([&] {
         check_ptr(ex, "exchange");
         check_ptr(form, "form");
-        const saccum_plan* p = ex->cs_self_accum.get();
-        *form = p ? ex->cs_self_form : 0;
-        if (n_boxes) *n_boxes = p ? int64_t(p->n_sum_boxes) : 0;
-        if (n_sources) *n_sources = p ? int64_t(p->srcs.size()) : 0;
-        if (n_field_sources) *n_field_sources = p ? int64_t(p->n_field_sources) : 0;
-        if (n_rotated_sources) *n_rotated_sources = p ? int64_t(p->n_rotated_sources) : 0;
+        const adjoint_set& set = ex->adjoint[exchange_plan::adj_cs_self];
+        *form = set.form;
+        saccum_counts(set.saccum.get(), n_boxes, n_sources, n_field_sources, n_rotated_sources);
         return GHX_OK;
     });
 }
-
-namespace
-{
-void check_cs_adjoint_self(const ghx_exchange* ex)
-{
-    check_ptr(ex, "exchange");
-    if (!ex->cs_self_accum)
-        throw invalid("fused cubed-sphere adjoint exchange: no plans (ghx_cs_exchange_adjoint_self_create)");
-    if (ex->dir_parity[0].word || ex->dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-}
-}  // namespace
 
 int ghx_cs_exchange_adjoint_self_plan(const ghx_exchange* ex, const ghx_saccum** out)
 {
     return guarded([&] {
         check_ptr(ex, "exchange");
         check_ptr(out, "out");
-        if (!ex->cs_self_accum)
-            throw invalid("fused cubed-sphere adjoint exchange: no plans (ghx_cs_exchange_adjoint_self_create)");
-        *out = ex->cs_self_accum.get();
+        *out = created_adjoint(ex, exchange_plan::adj_cs_self)->saccum.get();
         return GHX_OK;
     });
 }
@@ -1723,8 +1663,9 @@ int ghx_cs_exchange_adjoint_self_segments(const ghx_exchange* ex, int32_t* n_pac
 {
     return guarded([&] {
         check_ptr(ex, "exchange");
-        if (n_pack_segments) *n_pack_segments = ex->cs_self_pack ? ex->cs_self_pack->n_segments : 0;
-        if (n_pack_x_records) *n_pack_x_records = ex->cs_self_xpack ? ex->cs_self_xpack->n_records : 0;
+        const adjoint_set& set = ex->adjoint[exchange_plan::adj_cs_self];
+        if (n_pack_segments) *n_pack_segments = set.spack ? set.spack->n_segments : 0;
+        if (n_pack_x_records) *n_pack_x_records = set.xpack ? set.xpack->n_records : 0;
         return GHX_OK;
     });
 }
@@ -1745,28 +1686,15 @@ int ghx_saccum_source_map(const ghx_saccum* p, int64_t j, int64_t* strides, int3
 int ghx_cs_exchange_adjoint_self_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                       void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
 {
-    return guarded([&] {
-        check_cs_adjoint_self(ex);
-        if (n_recv < int32_t(ex->recv.size())) throw invalid("too few recv buffers");
-        // every message a self message: nothing to gather. Else the peer receive spaces alone, the
-        // transformed ones after the ordinary launch on the same stream
-        int rc = GHX_OK;
-        if (ex->cs_self_pack) rc = ex->cs_self_pack->execute(field_ptrs, n_fields, recv_buffers, n_recv, stream);
-        if (rc == GHX_OK && ex->cs_self_xpack)
-            rc = ex->cs_self_xpack->execute_pack(field_ptrs, n_fields, recv_buffers, n_recv, stream);
-        return rc;
-    });
+    return adjoint_pack(ex, exchange_plan::adj_cs_self, field_ptrs, n_fields, recv_buffers, n_recv, stream);
 }
 
 int ghx_cs_exchange_adjoint_self_accumulate(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
                                             void* const* send_buffers, int32_t n_send, int32_t zero_halos,
                                             ghx_stream stream)
 {
-    return guarded([&] {
-        check_cs_adjoint_self(ex);
-        if (n_send < int32_t(ex->send.size())) throw invalid("too few send buffers");
-        return ex->cs_self_accum->execute_get(field_ptrs, n_fields, send_buffers, n_send, zero_halos != 0, stream);
-    });
+    return adjoint_accumulate(ex, exchange_plan::adj_cs_self, field_ptrs, n_fields, send_buffers, n_send, zero_halos,
+                              stream);
 }
 
 int ghx_uput_segment(const ghx_put* put, int32_t k, ghx_uput_segment_info* out)

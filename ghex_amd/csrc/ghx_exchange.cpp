@@ -806,244 +806,224 @@ void exchange_plan::make_split()
     for (int dir = 0; dir < 2; ++dir) set_split_parity(dir);
 }
 
-void exchange_plan::make_adjoint(const int32_t* dtypes, int32_t n)
-{
-    if (!only_unstructured)
-        throw invalid("adjoint exchange: the exchange holds a structured or cubed-sphere item (their send "
-                      "boxes overlap; only index-list items have an adjoint)");
-    if (dir_parity[0].word || dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-    if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
-    std::vector<int32_t> dt;
-    for (const ghx_upack_entry& e : uentries[0]) dt.push_back(dtypes[e.field_slot]);
-    // a receive-only item names no contribution entry: its code is checked here
-    for (int32_t i = 0; i < n; ++i)
-        if (dtypes[i] < GHX_DT_F32 || dtypes[i] > GHX_DT_I64)
-            throw invalid("unknown dtype code " + std::to_string(dtypes[i]) + " (GHX_DT_F32, _F64, _I32, _I64)");
-    auto accum = std::make_unique<uaccum_plan>(uentries[0].data(), dt.data(), int(dt.size()), uentries[1].data(),
-                                               int(uentries[1].size()));
-    auto pack = std::make_unique<uplan>(uentries[1].data(), int(uentries[1].size()), 0);
-    adj_accum = std::move(accum);
-    adj_pack = std::move(pack);
-}
-
-void exchange_plan::make_sadjoint(const int32_t* dtypes, int32_t n)
-{
-    if (cubed_sphere)
-        throw invalid("adjoint exchange: the exchange holds a cubed-sphere item (its adjoint would rotate and "
-                      "flip signs; only regular structured items take ghx_sexchange_adjoint_create)");
-    if (!only_structured)
-        throw invalid("adjoint exchange: the exchange holds an unstructured item (an exchange mixing structured "
-                      "and unstructured items has no adjoint; index-list items take ghx_uexchange_adjoint_create)");
-    if (dir_parity[0].word || dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-    if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
-    // a receive-only item names no contribution entry: its code is checked here
-    for (int32_t i = 0; i < n; ++i)
-        if (dtypes[i] < GHX_DT_F32 || dtypes[i] > GHX_DT_I64)
-            throw invalid("unknown dtype code " + std::to_string(dtypes[i]) + " (GHX_DT_F32, _F64, _I32, _I64)");
-    std::vector<int32_t> dt;
-    for (const ghx_pack_entry& e : entries[0]) dt.push_back(dtypes[e.field_slot]);
-    auto accum = std::make_unique<saccum_plan>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
-                                               int(entries[1].size()));
-    auto pack = std::make_unique<splan>(entries[1].data(), int(entries[1].size()), 0);
-    sadj_accum = std::move(accum);
-    sadj_pack = std::move(pack);
-}
-
-void exchange_plan::make_sadjoint_self(const int32_t* dtypes, int32_t n)
-{
-    if (cubed_sphere)
-        throw invalid("adjoint exchange: the exchange holds a cubed-sphere item (its adjoint would rotate and "
-                      "flip signs; only regular structured items take ghx_sexchange_adjoint_self_create)");
-    if (!only_structured)
-        throw invalid("adjoint exchange: the exchange holds an unstructured item (an exchange mixing structured "
-                      "and unstructured items has no adjoint; index-list items take ghx_uexchange_adjoint_create)");
-    if (dir_parity[0].word || dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-    if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
-    for (int32_t i = 0; i < n; ++i)
-        if (dtypes[i] < GHX_DT_F32 || dtypes[i] > GHX_DT_I64)
-            throw invalid("unknown dtype code " + std::to_string(dtypes[i]) + " (GHX_DT_F32, _F64, _I32, _I64)");
-    // the receive entry at the same message bytes sources a self message's send entry
-    std::vector<int> recv_of_send(send.size(), -1);
-    for (size_t j = 0; j < send_of_recv.size(); ++j)
-        if (send_of_recv[j] >= 0) recv_of_send[size_t(send_of_recv[j])] = int(j);
-    std::vector<int32_t> dt;
-    std::vector<const ghx_pack_entry*> source;
-    std::vector<char> sourced(entries[1].size(), 0);
-    size_t n_self = 0;
-    for (const ghx_pack_entry& e : entries[0])
-    {
-        dt.push_back(dtypes[e.field_slot]);
-        source.push_back(nullptr);
-        const int j = recv_of_send[size_t(e.buffer_slot)];
-        if (j < 0) continue;
-        for (size_t k = 0; k < entries[1].size() && !source.back(); ++k)
-            if (entries[1][k].buffer_slot == j && entries[1][k].buffer_offset == e.buffer_offset)
-            {
-                source.back() = &entries[1][k];
-                sourced[k] = 1;
-            }
-        if (!source.back())
-            throw invalid("fused adjoint: a send entry of a self message has no receive entry at the same "
-                          "message bytes");
-        ++n_self;
-    }
-    if (n_self == 0) throw invalid("fused adjoint: the exchange has no self message (ghx_sexchange_adjoint_create)");
-    std::vector<ghx_pack_entry> peer;
-    for (size_t k = 0; k < entries[1].size(); ++k)
-    {
-        if (sourced[k]) continue;
-        if (send_of_recv[size_t(entries[1][k].buffer_slot)] >= 0)
-            throw invalid("fused adjoint: a receive entry of a self message has no send entry at the same "
-                          "message bytes");
-        peer.push_back(entries[1][k]);
-    }
-    auto accum = std::make_unique<saccum_plan>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
-                                               int(entries[1].size()), source.data());
-    std::unique_ptr<splan> pack;
-    if (!peer.empty()) pack = std::make_unique<splan>(peer.data(), int(peer.size()), 0);
-    sself_form = n_self == entries[0].size() && peer.empty() ? 1 : 2;
-    sself_accum = std::move(accum);
-    sself_pack = std::move(pack);
-}
-
 namespace
 {
-// what both cubed-sphere adjoint creates refuse of their arguments
-void check_cs_adjoint_args(const exchange_plan& ex, const int32_t* dtypes, int32_t n)
+using adjoint_kind = exchange_plan::adjoint_kind;
+
+// What every adjoint create refuses of its exchange and arguments: the items the kind does not
+// take, double-buffered buffers, and the dtype codes (a receive-only item names no contribution
+// entry: its code, and on the cubed sphere its size, is checked here).
+void check_adjoint_args(const exchange_plan& ex, adjoint_kind kind, const int32_t* dtypes, int32_t n)
 {
-    const int32_t n_items = ex.n_items;
-    const std::vector<int32_t>& cs_elem = ex.cs_elem;
-    const std::vector<ghx_cs_item>& cs_items = ex.cs_items;
-    if (!ex.cubed_sphere)
-        throw invalid("cubed-sphere adjoint exchange: not a cubed-sphere exchange (regular structured items take "
-                      "ghx_sexchange_adjoint_create, index-list items ghx_uexchange_adjoint_create)");
-    if (ex.dir_parity[0].word || ex.dir_parity[1].word)
-        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
-                      "(ghx_exchange_set_parity); its launches use one copy");
-    if (n != n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
+    const bool cs = kind == exchange_plan::adj_cs || kind == exchange_plan::adj_cs_self;
+    if (kind == exchange_plan::adj_list)
+    {
+        if (!ex.only_unstructured)
+            throw invalid("adjoint exchange: the exchange holds a structured or cubed-sphere item (their send "
+                          "boxes overlap; only index-list items have an adjoint)");
+    }
+    else if (cs)
+    {
+        if (!ex.cubed_sphere)
+            throw invalid("cubed-sphere adjoint exchange: not a cubed-sphere exchange (regular structured items take "
+                          "ghx_sexchange_adjoint_create, index-list items ghx_uexchange_adjoint_create)");
+    }
+    else
+    {
+        if (ex.cubed_sphere)
+            throw invalid(std::string("adjoint exchange: the exchange holds a cubed-sphere item (its adjoint would "
+                                      "rotate and flip signs; only regular structured items take ") +
+                          (kind == exchange_plan::adj_boxes ? "ghx_sexchange_adjoint_create)"
+                                                            : "ghx_sexchange_adjoint_self_create)"));
+        if (!ex.only_structured)
+            throw invalid("adjoint exchange: the exchange holds an unstructured item (an exchange mixing structured "
+                          "and unstructured items has no adjoint; index-list items take ghx_uexchange_adjoint_create)");
+    }
+    ex.check_single_buffered();
+    if (n != ex.n_items || !dtypes) throw invalid("adjoint exchange: one dtype code per exchange item");
     for (int32_t i = 0; i < n; ++i)
     {
         if (dtypes[i] < GHX_DT_F32 || dtypes[i] > GHX_DT_I64)
             throw invalid("unknown dtype code " + std::to_string(dtypes[i]) + " (GHX_DT_F32, _F64, _I32, _I64)");
-        // a receive-only item names no contribution entry: its size is checked here
+        if (!cs) continue;
         const int32_t size = (dtypes[i] == GHX_DT_F32 || dtypes[i] == GHX_DT_I32) ? 4 : 8;
-        if (size != cs_elem[size_t(i)])
+        if (size != ex.cs_elem[size_t(i)])
             throw invalid("cubed-sphere adjoint exchange: item " + std::to_string(i) + " has dtype code " +
                           std::to_string(dtypes[i]) + " (" + std::to_string(size) + " B) but elem_size " +
-                          std::to_string(cs_elem[size_t(i)]));
-        const int32_t kind = dtypes[i] <= GHX_DT_F64 ? 1 : 2;
-        if (cs_items[size_t(i)].is_vector && cs_items[size_t(i)].value_kind != kind)
+                          std::to_string(ex.cs_elem[size_t(i)]));
+        const ghx_cs_item& item = ex.cs_items[size_t(i)];
+        const int32_t value_kind = dtypes[i] <= GHX_DT_F64 ? 1 : 2;
+        if (item.is_vector && item.value_kind != value_kind)
             throw invalid("cubed-sphere adjoint exchange: vector item " + std::to_string(i) + " has value_kind " +
-                          std::to_string(cs_items[size_t(i)].value_kind) + " but dtype code " +
-                          std::to_string(dtypes[i]) + " (1: GHX_DT_F32 / _F64, 2: GHX_DT_I32 / _I64)");
+                          std::to_string(item.value_kind) + " but dtype code " + std::to_string(dtypes[i]) +
+                          " (1: GHX_DT_F32 / _F64, 2: GHX_DT_I32 / _I64)");
     }
+}
+
+// The self messages of an exchange, entry by entry: the receive entry at the same message bytes
+// sources a self message's send entry.
+struct self_match
+{
+    std::vector<int> recv_of;  // per send entry: its receive entry, -1 for a peer message's
+    std::vector<size_t> peer;  // the receive entries of the peer messages
+    size_t n_self = 0;
+};
+
+// throws unless every entry of a self message has its counterpart and there is a self message;
+// `plain_create` names the create that serves an exchange without one
+self_match match_self_messages(const exchange_plan& ex, const char* plain_create)
+{
+    const std::vector<ghx_pack_entry>&se = ex.entries[0], &re = ex.entries[1];
+    std::vector<int> recv_of_send(ex.send.size(), -1);
+    for (size_t j = 0; j < ex.send_of_recv.size(); ++j)
+        if (ex.send_of_recv[j] >= 0) recv_of_send[size_t(ex.send_of_recv[j])] = int(j);
+    self_match m;
+    std::vector<char> sourced(re.size(), 0);
+    for (const ghx_pack_entry& e : se)
+    {
+        m.recv_of.push_back(-1);
+        const int j = recv_of_send[size_t(e.buffer_slot)];
+        if (j < 0) continue;
+        for (size_t k = 0; k < re.size() && m.recv_of.back() < 0; ++k)
+            if (re[k].buffer_slot == j && re[k].buffer_offset == e.buffer_offset) m.recv_of.back() = int(k);
+        if (m.recv_of.back() < 0)
+            throw invalid("fused adjoint: a send entry of a self message has no receive entry at the same "
+                          "message bytes");
+        sourced[size_t(m.recv_of.back())] = 1;
+        ++m.n_self;
+    }
+    if (m.n_self == 0)
+        throw invalid(std::string("fused adjoint: the exchange has no self message (") + plain_create + ")");
+    for (size_t k = 0; k < re.size(); ++k)
+    {
+        if (sourced[k]) continue;
+        if (ex.send_of_recv[size_t(re[k].buffer_slot)] >= 0)
+            throw invalid("fused adjoint: a receive entry of a self message has no send entry at the same "
+                          "message bytes");
+        m.peer.push_back(k);
+    }
+    return m;
 }
 }  // namespace
 
-void exchange_plan::make_cs_adjoint(const int32_t* dtypes, int32_t n)
+void exchange_plan::check_single_buffered() const
 {
-    check_cs_adjoint_args(*this, dtypes, n);
-    std::vector<int32_t> dt;
-    for (const ghx_pack_entry& e : entries[0]) dt.push_back(dtypes[e.field_slot]);
-    auto accum = std::make_unique<::ghx_saccum>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
-                                               int(entries[1].size()));
-    std::unique_ptr<splan> pack;
-    if (!cs_segs.empty()) pack = std::make_unique<splan>(cs_segs, cs_gf, cs_gb, cs_sbytes, 0);
-    cs_adj_accum = std::move(accum);
-    cs_adj_pack = std::move(pack);
-    cs_adj_ready = true;
+    if (dir_parity[0].word || dir_parity[1].word)
+        throw invalid("adjoint exchange: the exchange has double-buffered buffers "
+                      "(ghx_exchange_set_parity); its launches use one copy");
 }
 
-void exchange_plan::make_cs_adjoint_self(const int32_t* dtypes, int32_t n)
+void exchange_plan::make_adjoint(adjoint_kind kind, const int32_t* dtypes, int32_t n)
 {
-    check_cs_adjoint_args(*this, dtypes, n);
-    // the receive entry at the same message bytes sources a self message's send entry (the match
-    // of make_sadjoint_self), box k of one with box k of the other as build_cs_self pairs them
-    std::vector<int> recv_of_send(send.size(), -1);
-    for (size_t j = 0; j < send_of_recv.size(); ++j)
-        if (send_of_recv[j] >= 0) recv_of_send[size_t(send_of_recv[j])] = int(j);
+    check_adjoint_args(*this, kind, dtypes, n);
+    adjoint_set set;
+    set.form = 1;
+    if (kind == adj_list)
+    {
+        std::vector<int32_t> dt;
+        for (const ghx_upack_entry& e : uentries[0]) dt.push_back(dtypes[e.field_slot]);
+        set.uaccum = std::make_unique<uaccum_plan>(uentries[0].data(), dt.data(), int(dt.size()), uentries[1].data(),
+                                                   int(uentries[1].size()));
+        set.upack = std::make_unique<uplan>(uentries[1].data(), int(uentries[1].size()), 0);
+        adjoint[kind] = std::move(set);
+        return;
+    }
+    const std::vector<ghx_pack_entry>&se = entries[0], &re = entries[1];
     std::vector<int32_t> dt;
-    std::vector<const ghx_pack_entry*> source;
-    std::vector<std::vector<xseg>> spaces(entries[0].size());
-    std::vector<const xseg*> space;
-    std::vector<char> sourced(entries[1].size(), 0);
-    size_t n_self = 0;
-    for (size_t e = 0; e < entries[0].size(); ++e)
+    for (const ghx_pack_entry& e : se) dt.push_back(dtypes[e.field_slot]);
+    auto accum = [&](const ghx_pack_entry* const* source, const xseg* const* space) {
+        return std::make_unique<::ghx_saccum>(se.data(), dt.data(), int(dt.size()), re.data(), int(re.size()), source,
+                                             space);
+    };
+    if (kind == adj_boxes)
     {
-        const ghx_pack_entry& se = entries[0][e];
-        dt.push_back(dtypes[se.field_slot]);
-        source.push_back(nullptr);
-        space.push_back(nullptr);
-        const int j = recv_of_send[size_t(se.buffer_slot)];
-        if (j < 0) continue;
-        size_t k = 0;
-        for (; k < entries[1].size(); ++k)
-            if (entries[1][k].buffer_slot == j && entries[1][k].buffer_offset == se.buffer_offset) break;
-        if (k == entries[1].size())
-            throw invalid("fused adjoint: a send entry of a self message has no receive entry at the same "
-                          "message bytes");
-        const ghx_pack_entry& re = entries[1][k];
-        const halo_entry& he = cs_rhalos[k];
-        if (int(he.boxes.size()) != re.n_boxes || re.n_boxes != se.n_boxes)
-            throw invalid("fused adjoint: contribution entry " + std::to_string(e) +
-                          " and its source differ in their number of boxes");
-        for (size_t b = 0; b < he.boxes.size(); ++b)
-            spaces[e].push_back(cs_space_box(re.field, cs_items[size_t(re.field_slot)], he.boxes[b], he.tiles[b],
-                                             re.field_slot, re.buffer_slot, 0));
-        source.back() = &re;
-        space.back() = spaces[e].data();
-        sourced[k] = 1;
-        ++n_self;
+        set.saccum = accum(nullptr, nullptr);
+        set.spack = std::make_unique<splan>(re.data(), int(re.size()), 0);
     }
-    if (n_self == 0)
-        throw invalid("fused adjoint: the exchange has no self message (ghx_cs_exchange_adjoint_create)");
-    std::vector<char> peer_buf(recv.size(), 0);
-    bool any_peer = false;
-    for (size_t k = 0; k < entries[1].size(); ++k)
+    else if (kind == adj_cs)
     {
-        if (sourced[k]) continue;
-        if (send_of_recv[size_t(entries[1][k].buffer_slot)] >= 0)
-            throw invalid("fused adjoint: a receive entry of a self message has no send entry at the same "
-                          "message bytes");
-        peer_buf[size_t(entries[1][k].buffer_slot)] = 1;
-        any_peer = true;
+        set.saccum = accum(nullptr, nullptr);
+        if (!cs_segs.empty()) set.spack = std::make_unique<splan>(cs_segs, cs_gf, cs_gb, cs_sbytes, 0);
+        set.xpack = xunpack.get();
     }
-    auto accum = std::make_unique<::ghx_saccum>(entries[0].data(), dt.data(), int(dt.size()), entries[1].data(),
-                                               int(entries[1].size()), source.data(), space.data());
-    // the reverse pack of the peer receive spaces: the kept ordinary segments and the transformed
-    // boxes whose receive buffer is a peer's
-    std::unique_ptr<splan> pack;
-    std::unique_ptr<xplan> xpack;
-    if (any_peer)
+    else
     {
-        std::vector<seg_s> segs;
-        std::vector<int32_t> gf, gb;
-        uint64_t bytes = 0;
-        for (size_t i = 0; i < cs_segs.size(); ++i)
-            if (peer_buf[size_t(cs_gb[i])])
-            {
-                segs.push_back(cs_segs[i]);
-                gf.push_back(cs_gf[i]);
-                gb.push_back(cs_gb[i]);
-                bytes += cs_segs[i].bytes;
-            }
-        if (!segs.empty()) pack = std::make_unique<splan>(std::move(segs), gf, gb, bytes, 0);
-        std::vector<xseg> boxes;
-        if (xunpack)
-            for (const xseg& b : xunpack->boxes)
-                if (peer_buf[size_t(b.buf_slot)]) boxes.push_back(b);
-        if (!boxes.empty()) xpack = std::make_unique<xplan>(std::move(boxes));
+        const bool cs = kind == adj_cs_self;
+        const self_match m =
+            match_self_messages(*this, cs ? "ghx_cs_exchange_adjoint_create" : "ghx_sexchange_adjoint_create");
+        std::vector<const ghx_pack_entry*> source(se.size(), nullptr);
+        // cubed sphere: the receiving side of each box of a paired entry, box k of one with box k of
+        // the other as build_cs_self pairs them
+        std::vector<std::vector<xseg>> spaces(se.size());
+        std::vector<const xseg*> space(se.size(), nullptr);
+        for (size_t e = 0; e < se.size(); ++e)
+        {
+            if (m.recv_of[e] < 0) continue;
+            const ghx_pack_entry& r = re[size_t(m.recv_of[e])];
+            source[e] = &r;
+            if (!cs) continue;
+            const halo_entry& he = cs_rhalos[size_t(m.recv_of[e])];
+            if (int(he.boxes.size()) != r.n_boxes || r.n_boxes != se[e].n_boxes)
+                throw invalid("fused adjoint: contribution entry " + std::to_string(e) +
+                              " and its source differ in their number of boxes");
+            for (size_t b = 0; b < he.boxes.size(); ++b)
+                spaces[e].push_back(cs_space_box(r.field, cs_items[size_t(r.field_slot)], he.boxes[b], he.tiles[b],
+                                                 r.field_slot, r.buffer_slot, 0));
+            space[e] = spaces[e].data();
+        }
+        set.saccum = accum(source.data(), cs ? space.data() : nullptr);
+        // the reverse pack of the peer receive entries alone
+        if (!cs && !m.peer.empty())
+        {
+            std::vector<ghx_pack_entry> peer;
+            for (size_t k : m.peer) peer.push_back(re[k]);
+            set.spack = std::make_unique<splan>(peer.data(), int(peer.size()), 0);
+        }
+        // cubed sphere: the kept ordinary segments and the transformed boxes whose receive buffer
+        // is a peer's
+        if (cs && !m.peer.empty())
+        {
+            std::vector<char> peer_buf(recv.size(), 0);
+            for (size_t k : m.peer) peer_buf[size_t(re[k].buffer_slot)] = 1;
+            std::vector<seg_s> segs;
+            std::vector<int32_t> gf, gb;
+            uint64_t bytes = 0;
+            for (size_t i = 0; i < cs_segs.size(); ++i)
+                if (peer_buf[size_t(cs_gb[i])])
+                {
+                    segs.push_back(cs_segs[i]);
+                    gf.push_back(cs_gf[i]);
+                    gb.push_back(cs_gb[i]);
+                    bytes += cs_segs[i].bytes;
+                }
+            if (!segs.empty()) set.spack = std::make_unique<splan>(std::move(segs), gf, gb, bytes, 0);
+            std::vector<xseg> boxes;
+            if (xunpack)
+                for (const xseg& b : xunpack->boxes)
+                    if (peer_buf[size_t(b.buf_slot)]) boxes.push_back(b);
+            if (!boxes.empty()) set.own_xpack = std::make_unique<xplan>(std::move(boxes));
+            set.xpack = set.own_xpack.get();
+        }
+        set.form = m.n_self == se.size() && m.peer.empty() ? 1 : 2;
     }
-    cs_self_form = n_self == entries[0].size() && !any_peer ? 1 : 2;
-    cs_self_accum = std::move(accum);
-    cs_self_pack = std::move(pack);
-    cs_self_xpack = std::move(xpack);
+    adjoint[kind] = std::move(set);
+}
+
+int exchange_plan::adjoint_set::pack(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const
+{
+    int rc = GHX_OK;
+    if (upack) rc = upack->execute(fptr, nf, bptr, nb, stream);
+    else if (spack) rc = spack->execute(fptr, nf, bptr, nb, stream);
+    if (rc == GHX_OK && xpack) rc = xpack->execute_pack(fptr, nf, bptr, nb, stream);
+    return rc;
+}
+
+int exchange_plan::adjoint_set::accumulate(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos,
+                                           void* stream) const
+{
+    if (uaccum) return uaccum->execute(fptr, nf, bptr, nb, zero_halos, stream);
+    return saccum->get ? saccum->execute_get(fptr, nf, bptr, nb, zero_halos, stream)
+                       : saccum->execute(fptr, nf, bptr, nb, zero_halos, stream);
 }
 
 int exchange_plan::execute_buffer(int dir, int b, void* const* fptr, int nf, void* const* bptr,

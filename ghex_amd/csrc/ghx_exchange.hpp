@@ -74,58 +74,66 @@ struct exchange_plan
     std::unique_ptr<uput_plan> umixed;
     std::unique_ptr<uplan> upunpack;
     std::string umixed_reason;
-    // the adjoint of an exchange of unstructured items (ghx_uexchange_adjoint_create): the reverse
-    // pack, a pack plan over uentries[1] that gathers the halo cells into the receive buffers, and
-    // the accumulate plan (k_accum_u) with uentries[0] as contribution entries and uentries[1] as
-    // zero entries. Both null until created.
+    // The adjoint of the exchange: one plan set per kind, created on demand by
+    // make_adjoint and independent of each other (the plain and the fused form of one exchange
+    // coexist). The reverse pack gathers the halo cells into the receive buffers, the accumulate
+    // adds the send buffers' contributions into their owners.
+    //  list (ghx_uexchange_adjoint_create): a pack plan over uentries[1]; k_accum_u with uentries[0]
+    //   as contribution entries and uentries[1] as zero entries.
+    //  boxes (ghx_sexchange_adjoint_create): the same over entries[1] and entries[0] (k_accum_s).
+    //  boxes_self (ghx_sexchange_adjoint_self_create): the self messages fused. The get plan
+    //   (k_accum_get_s) reads a self message from the receiving field's halo cells, and the reverse
+    //   pack covers the peer receive entries alone.
+    //  cs (ghx_cs_exchange_adjoint_create): the reverse pack is the transpose of the unpack in its two
+    //   parts: a pack plan over the ordinary receive segments (cs_segs: a copy of what sunpack was
+    //   built from) and k_pack_x over xunpack's own records (no second tiler, no second upload). The
+    //   accumulate plan is that of boxes: the send side of a cubed-sphere exchange is ordinary boxes
+    //   of the sender's field.
+    //  cs_self (ghx_cs_exchange_adjoint_self_create): the get plan (k_accum_get_x) reads a self message
+    //   from the receiving field's halo cells through the edge's transform, and the reverse pack
+    //   covers the peer receive spaces alone: the kept ordinary segments and xunpack's boxes filtered
+    //   by receive buffer.
+    enum adjoint_kind { adj_list, adj_boxes, adj_boxes_self, adj_cs, adj_cs_self, n_adjoint_kinds };
+    struct adjoint_set
+    {
+        // 0 not created; 1 created (a fused set: every message is a self message); 2 a fused set
+        // with self and peer messages
+        int32_t form = 0;
+        // the reverse pack: at most one ordinary plan and at most one transformed pack, which the
+        // set owns (cs_self) or borrows from the exchange's xunpack (cs). All null: nothing to gather
+        std::unique_ptr<splan> spack;
+        std::unique_ptr<uplan> upack;
+        std::unique_ptr<xplan> own_xpack;
+        const xplan* xpack = nullptr;
+        // the accumulate plan: uaccum for list, else saccum (the handle type: the cubed-sphere
+        // *_plan calls lend it); a get plan in the fused sets
+        std::unique_ptr<uaccum_plan> uaccum;
+        std::unique_ptr<::ghx_saccum> saccum;
+        // the ordinary launch, then the transformed one on the same stream
+        int pack(void* const* fptr, int nf, void* const* bptr, int nb, void* stream) const;
+        int accumulate(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
+    };
+    adjoint_set adjoint[n_adjoint_kinds];
+    // throws `invalid` and leaves adjoint[kind] as it was
+    void make_adjoint(adjoint_kind kind, const int32_t* dtypes, int32_t n);
+    // both launches of an adjoint use one copy of each buffer: its creates and launches refuse an
+    // exchange with double-buffered buffers (ghx_exchange_set_parity)
+    void check_single_buffered() const;
     bool only_unstructured = true;  // every item is an index-list item (set by make_exchange)
-    std::unique_ptr<uplan> adj_pack;
-    std::unique_ptr<uaccum_plan> adj_accum;
-    void make_adjoint(const int32_t* dtypes, int32_t n);
-    // the adjoint of an exchange of regular structured items (ghx_sexchange_adjoint_create): the
-    // reverse pack, a pack plan over entries[1], and the accumulate plan (k_accum_s) with entries[0]
-    // as contribution entries and entries[1] as zero entries. Both null until created.
     bool only_structured = true;  // every item is a regular structured item (set by make_exchange)
     bool cubed_sphere = false;    // made by ghx_cs_exchange_create
-    std::unique_ptr<splan> sadj_pack;
-    std::unique_ptr<saccum_plan> sadj_accum;
-    void make_sadjoint(const int32_t* dtypes, int32_t n);
-    // the same adjoint with the self messages fused (ghx_sexchange_adjoint_self_create): the get
-    // plan (k_accum_get_s) reads a self message from the receiving field's halo cells, and the
-    // reverse pack covers the peer receive entries alone (null: every message is a self message).
     // send_of_recv: per recv buffer the send buffer of the same self message or -1 (self_pairs,
-    // the match of build_mixed), set by make_exchange. form: 0 none, 1 all self, 2 mixed.
+    // the match of build_mixed), set by make_exchange.
     std::vector<int> send_of_recv;
-    int32_t sself_form = 0;
-    std::unique_ptr<splan> sself_pack;
-    std::unique_ptr<saccum_plan> sself_accum;
-    void make_sadjoint_self(const int32_t* dtypes, int32_t n);
-    // the adjoint of a cubed-sphere exchange (ghx_cs_exchange_adjoint_create). The
-    // reverse pack is the transpose of the unpack in its two parts: a pack plan over the ordinary
-    // receive segments (cs_segs: a copy of what sunpack was built from) and k_pack_x over xunpack's
-    // own records (no second tiler, no second upload). The accumulate plan is make_sadjoint's: the
-    // send side of a cubed-sphere exchange is ordinary boxes of the sender's field. ready: created.
+    // cubed sphere: the ordinary receive segments with their caller slots and bytes, the items with
+    // their element sizes, and cs_rhalos: a copy of the halo entry (boxes in both coordinates,
+    // tiles) behind each of entries[1], kept by make_exchange
     std::vector<seg_s> cs_segs;
     std::vector<int32_t> cs_gf, cs_gb;
     uint64_t cs_sbytes = 0;
     std::vector<ghx_cs_item> cs_items;  // per item, with its element size
     std::vector<int32_t> cs_elem;
-    bool cs_adj_ready = false;
-    std::unique_ptr<splan> cs_adj_pack;  // null: no ordinary receive segment
-    std::unique_ptr<::ghx_saccum> cs_adj_accum;  // the handle type: ghx_cs_exchange_adjoint_plan lends it
-    void make_cs_adjoint(const int32_t* dtypes, int32_t n);
-    // the same adjoint with the self messages fused (ghx_cs_exchange_adjoint_self_create, DESIGN.md
-    // §4.8): the get plan (k_accum_get_x) reads a self message from the receiving field's halo cells
-    // through the edge's transform, and the reverse pack covers the peer receive spaces alone: the
-    // kept ordinary segments and xunpack's boxes filtered by receive buffer (both null: every
-    // message is a self message). cs_rhalos: a copy of the halo entry (boxes in both coordinates,
-    // tiles) behind each of entries[1], kept by make_exchange. form: 0 none, 1 all self, 2 mixed.
     std::vector<halo_entry> cs_rhalos;
-    int32_t cs_self_form = 0;
-    std::unique_ptr<splan> cs_self_pack;
-    std::unique_ptr<xplan> cs_self_xpack;
-    std::unique_ptr<::ghx_saccum> cs_self_accum;
-    void make_cs_adjoint_self(const int32_t* dtypes, int32_t n);
 
     void make_split();  // the per-buffer plans (ghx_exchange_split)
 

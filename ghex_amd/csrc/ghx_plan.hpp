@@ -363,7 +363,11 @@ struct saccum_plan
     saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, int n, const ghx_pack_entry* zero,
                 int n_zero, const ghx_pack_entry* const* source = nullptr, const xseg* const* space = nullptr);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
+    // a get plan's launch (ghx_saccum_get_execute); each of the two refuses the other kind of plan
     int execute_get(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
+
+private:
+    int launch(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
 };
 
 // The per-call entry points' plans, cached by content (ghx_cache.cpp): the plan of the call's

@@ -556,47 +556,26 @@ saccum_plan::saccum_plan(const ghx_pack_entry* contrib, const int32_t* dtypes, i
 
 int saccum_plan::execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const
 {
-    const uint32_t n_tiles = zero_halos ? uint32_t(tiles.size()) : n_sum_tiles;
     if (get) throw invalid("a get plan (ghx_saccum_get_create) runs through ghx_saccum_get_execute");
-    if (n_tiles == 0) return GHX_OK;
-    if (!fptr || (!bptr && max_buf_slot >= 0) || nf <= max_field_slot || nb <= max_buf_slot)
-        throw invalid("pointer arrays do not cover the plan's slots");
-    kargs_sa a{};
-    a.n_tiles = n_tiles;
-    for (int s = 0; s <= max_field_slot; ++s)
-    {
-        if (!slot_elem[s]) continue;
-        if (!fptr[s]) throw invalid("null field pointer");
-        a.field_ptr[s] = reinterpret_cast<uint64_t>(fptr[s]);
-        if (a.field_ptr[s] % slot_elem[s]) throw invalid("a field pointer is not aligned to its element");
-    }
-    for (int b = 0; b <= max_buf_slot; ++b)
-    {
-        if (!buf_elem[b]) continue;
-        if (!bptr[b]) throw invalid("null buffer pointer");
-        a.buf_ptr[b] = reinterpret_cast<uint64_t>(bptr[b]);
-        if (a.buf_ptr[b] % buf_elem[b]) throw invalid("a buffer pointer is not aligned to its elements");
-        if (a.buf_ptr[b] % 8) a.buf_mis8 |= uint64_t(1) << b;
-        if (a.buf_ptr[b] % 16) a.buf_mis16 |= uint64_t(1) << b;
-    }
-    if (!dev.tiles) throw hip_error("plan has no device tables (no HIP device at creation)");
-    a.tiles = static_cast<const sacc_tile*>(dev.tiles);
-    a.srcs = static_cast<const sacc_src*>(dev.srcs);
-    return launch_accum_s(a, stream, grid_for_tiles(n_tiles));
+    return launch(fptr, nf, bptr, nb, zero_halos, stream);
 }
 
-// k_accum_get_s (k_accum_get_x: a plan with cubed-sphere spaces): the source pointer table holds the
-// buffers that are read, then the source fields
 int saccum_plan::execute_get(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const
 {
     if (!get) throw invalid("not a get plan (ghx_saccum_get_create)");
+    return launch(fptr, nf, bptr, nb, zero_halos, stream);
+}
+
+// k_accum_s, or of a get plan k_accum_get_s (k_accum_get_x: a plan with cubed-sphere spaces)
+int saccum_plan::launch(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const
+{
     const uint32_t n_tiles = zero_halos ? uint32_t(tiles.size()) : n_sum_tiles;
     if (n_tiles == 0) return GHX_OK;
     if (!fptr || (!bptr && max_buf_slot >= 0) || nf <= max_field_slot || nb <= max_buf_slot)
         throw invalid("pointer arrays do not cover the plan's slots");
     kargs_sa a{};
     a.n_tiles = n_tiles;
-    a.zero_src = zero_halos ? 1 : 0;
+    a.zero_src = get && zero_halos ? 1 : 0;
     for (int s = 0; s <= max_field_slot; ++s)
     {
         if (!slot_elem[s]) continue;
@@ -604,12 +583,16 @@ int saccum_plan::execute_get(void* const* fptr, int nf, void* const* bptr, int n
         a.field_ptr[s] = reinterpret_cast<uint64_t>(fptr[s]);
         if (a.field_ptr[s] % slot_elem[s]) throw invalid("a field pointer is not aligned to its element");
     }
-    for (uint32_t t = 0; t < uint32_t(tab_slot.size()); ++t)
+    // the source pointer table: the buffers at their own slots, or a get plan's tab_slot (the
+    // buffers that are read, then the source fields)
+    const uint32_t n_tab = get ? uint32_t(tab_slot.size()) : uint32_t(max_buf_slot + 1);
+    for (uint32_t t = 0; t < n_tab; ++t)
     {
-        const int32_t s = tab_slot[t];
-        if (t >= tab_field) a.buf_ptr[t] = a.field_ptr[s];  // checked above
+        const int32_t s = get ? tab_slot[t] : int32_t(t);
+        if (get && t >= tab_field) a.buf_ptr[t] = a.field_ptr[s];  // checked above
         else
         {
+            if (!buf_elem[s]) continue;  // a buffer no entry reads (tab_slot names none)
             if (!bptr[s]) throw invalid("null buffer pointer");
             a.buf_ptr[t] = reinterpret_cast<uint64_t>(bptr[s]);
             if (a.buf_ptr[t] % buf_elem[s]) throw invalid("a buffer pointer is not aligned to its elements");
@@ -620,8 +603,9 @@ int saccum_plan::execute_get(void* const* fptr, int nf, void* const* bptr, int n
     if (!dev.tiles) throw hip_error("plan has no device tables (no HIP device at creation)");
     a.tiles = static_cast<const sacc_tile*>(dev.tiles);
     a.srcs = static_cast<const sacc_src*>(dev.srcs);
-    return rotated ? launch_accum_get_x(a, stream, grid_for_tiles(n_tiles))
-                   : launch_accum_get_s(a, stream, grid_for_tiles(n_tiles));
+    const uint32_t grid = grid_for_tiles(n_tiles);
+    if (!get) return launch_accum_s(a, stream, grid);
+    return rotated ? launch_accum_get_x(a, stream, grid) : launch_accum_get_s(a, stream, grid);
 }
 
 }  // namespace ghx

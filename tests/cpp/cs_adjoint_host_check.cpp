@@ -1,7 +1,7 @@
 // cs_adjoint_host_check — stand-alone host program (its own main; links the library's sources) for
 // the reverse pack of the cubed-sphere adjoint exchange. It plans the cubed-sphere fixture
 // geometries with all domains on one rank (ghx_cs_pattern_create, ghx_cs_exchange_create, no
-// device), attaches the adjoint plans (exchange_plan::make_cs_adjoint; the accumulate's 64-slot
+// device), attaches the adjoint plans (exchange_plan::make_adjoint; the accumulate's 64-slot
 // limit refuses the 24-domain geometry, whose reverse pack is replayed all the same) and replays
 // on the host, with the kernels' own address arithmetic (ghx_addr.hpp) exactly as k_pack_x and
 // k_copy<true, seg_s> index them, every seg_x tile record of the transformed unpack plan with the
@@ -58,14 +58,15 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, i
         {
             CHECK(nxr == (ex->xunpack ? ex->xunpack->n_records : 0));
             CHECK(nxt == (ex->xunpack ? int32_t(ex->xunpack->n_tiles) : 0));
-            CHECK(bool(ex->cs_adj_pack) == bool(ex->sunpack));
+            CHECK(bool(ex->adjoint[exchange_plan::adj_cs].spack) == bool(ex->sunpack));
         }
     }
     // the ordinary reverse pack of an exchange without adjoint plans: built as create builds it
     std::unique_ptr<splan> own_pack;
-    if (!ex->cs_adj_pack && !ex->cs_segs.empty())
+    const std::unique_ptr<splan>& adj_pack = ex->adjoint[exchange_plan::adj_cs].spack;
+    if (!adj_pack && !ex->cs_segs.empty())
         own_pack = std::make_unique<splan>(ex->cs_segs, ex->cs_gf, ex->cs_gb, ex->cs_sbytes, 0);
-    const splan* pack = ex->cs_adj_pack ? ex->cs_adj_pack.get() : own_pack.get();
+    const splan* pack = adj_pack ? adj_pack.get() : own_pack.get();
     CHECK(bool(pack) == bool(ex->sunpack));
     if (pack && ex->sunpack) CHECK(pack->n_segments == ex->sunpack->n_segments && pack->bytes == ex->sunpack->bytes);
 

@@ -87,13 +87,14 @@ void run(const config& cfg, const int* layout, const std::vector<spec>& specs, b
     int64_t n_boxes = 0, n_sources = 0, n_fs = 0, n_rot = 0;
     CHECK(ghx_cs_exchange_adjoint_self_info(ex, &form, &n_boxes, &n_sources, &n_fs, &n_rot) == GHX_OK);
     CHECK(form == (two_ranks ? 2 : 1) && n_boxes > 0 && n_rot > 0);
-    CHECK(bool(ex->cs_self_pack || ex->cs_self_xpack) == two_ranks);
-    if (rc != GHX_OK || !ex->cs_self_accum)
+    const exchange_plan::adjoint_set& set = ex->adjoint[exchange_plan::adj_cs_self];
+    CHECK(bool(set.spack || set.xpack) == two_ranks);
+    if (rc != GHX_OK || !set.saccum)
     {
         ghx_exchange_destroy(ex);
         return;
     }
-    const saccum_plan& p = *ex->cs_self_accum;
+    const saccum_plan& p = *set.saccum;
     CHECK(p.get && p.rotated);
 
     // the send buffers: what the peers' reverse packs would have delivered

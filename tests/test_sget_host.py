@@ -294,6 +294,61 @@ def test_self_plans_of_an_exchange(ghx):
     ghx.call("ghx_exchange_set_parity", plan.h, 0, None, 0, None, 0)
 
 
+def _plain_info(ghx, plan):
+    r, nb, ns = ctypes.c_int32(-1), ctypes.c_int64(-1), ctypes.c_int64(-1)
+    ghx.call("ghx_sexchange_adjoint_info", plan.h, ctypes.byref(r), ctypes.byref(nb), ctypes.byref(ns))
+    return r.value, nb.value, ns.value
+
+
+def test_a_refused_create_leaves_the_plans_it_would_have_replaced(ghx):
+    """One periodic domain, N = 6, H = 2: the plain adjoint survives two refused creates as it was,
+    the fused form is created beside it, and a refused create of that one leaves both."""
+    from tests.test_saccum_host import _exchange
+    L = ghx.lib()
+    plan = _exchange(ghx, [cube(6, 2)], 6, 2)
+    ghx.call("ghx_sexchange_adjoint_create", plan.h, ghx.i32_array([F64]), 1)
+    plain = _plain_info(ghx, plan)
+    assert plain == (1, 26, 6 + 12 * 3 + 8 * 7)
+    assert L.ghx_sexchange_adjoint_create(plan.h, ghx.i32_array([7]), 1) == -1
+    assert b"unknown dtype code 7" in L.ghx_last_error()
+    assert L.ghx_sexchange_adjoint_create(plan.h, ghx.i32_array([F64, F64]), 2) == -1
+    assert b"one dtype code per exchange item" in L.ghx_last_error()
+    assert _plain_info(ghx, plan) == plain
+    assert _self_info(ghx, plan) == (0, 0, 0, 0)
+    ghx.call("ghx_sexchange_adjoint_self_create", plan.h, ghx.i32_array([F64]), 1)
+    fused = _self_info(ghx, plan)
+    assert fused == (1, 26, 6 + 12 * 3 + 8 * 7, 1)
+    assert _plain_info(ghx, plan) == plain
+    assert L.ghx_sexchange_adjoint_self_create(plan.h, ghx.i32_array([7]), 1) == -1
+    assert L.ghx_sexchange_adjoint_self_create(plan.h, ghx.i32_array([F64, F64]), 2) == -1
+    assert (_plain_info(ghx, plan), _self_info(ghx, plan)) == (plain, fused)
+
+
+def test_a_refused_create_leaves_the_cubed_sphere_plans(ghx):
+    """The same on the c = 6 cube on one rank, with ghx_cs_exchange_adjoint_create and _self_create."""
+    from tests import cs_cases
+    from tests import cs_get_cases as G
+    ex = G.Exchange(ghx, cs_cases.config(6), G.TWO)
+    good = ex.codes()
+    try:
+        assert ex.create_unfused() == 0, ex.error()
+        plain = ex.unfused_info()
+        assert plain["ready"] == 1 and plain["boxes"] > 0 and plain["sources"] > 0 and plain["x_records"] > 0
+        assert ex.create_unfused([7] + good[1:]) == -1 and "unknown dtype code 7" in ex.error()
+        assert ex.create_unfused(good[:-1]) == -1 and "one dtype code per exchange item" in ex.error()
+        assert ex.unfused_info() == plain
+        assert ex.info()["form"] == 0
+        assert ex.create() == 0, ex.error()
+        fused = ex.info()
+        assert fused["form"] == 1 and (fused["boxes"], fused["sources"]) == (plain["boxes"], plain["sources"])
+        assert fused["field_sources"] > 0
+        assert ex.unfused_info() == plain
+        assert ex.create([7] + good[1:]) == -1 and ex.create(good[:-1]) == -1
+        assert (ex.unfused_info(), ex.info()) == (plain, fused)
+    finally:
+        ex.close()
+
+
 def test_an_exchange_without_a_self_message_is_refused(ghx):
     """(2,1,1) not periodic: every message of a rank goes to its peer."""
     from ghex_amd.communication_object import _ExchangePlan
