@@ -167,6 +167,11 @@ _SIGS = {
     "ghx_uaccum_contrib": (c_i32, [c_vp, c_i64, P(c_i32), P(c_i64)]),
     "ghx_uaccum_destroy": (c_i32, [c_vp]),
     "ghx_uexchange_adjoint_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64)]),
+    "ghx_uaccum_get_create": (c_i32, [P(UPackEntry), P(c_i32), P(P(UPackEntry)), c_i32, P(UPackEntry), c_i32,
+                                      P(c_vp)]),
+    "ghx_uaccum_get_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
+    "ghx_uaccum_contrib_kind": (c_i32, [c_vp, c_i64, P(c_i32), P(c_i32), P(c_i64)]),
+    "ghx_uexchange_adjoint_self_info": (c_i32, [c_vp, P(c_i32), P(c_i64), P(c_i64), P(c_i64)]),
     "ghx_saccum_create": (c_i32, [P(PackEntry), P(c_i32), c_i32, P(PackEntry), c_i32, P(c_vp)]),
     "ghx_saccum_execute": (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp]),
     "ghx_saccum_info": (c_i32, [c_vp, P(c_u64), P(c_i64), P(c_i64), P(c_i64), P(c_i64), P(c_i32)]),
@@ -267,9 +272,9 @@ _SIGS = {
     "ghx_copier_acquire": (c_i32, [c_vp, c_vp]),
     "ghx_copier_destroy": (c_i32, [c_vp]),
 }
-# the five adjoint families' create, reverse pack and accumulate take the same arguments
-for _prefix in ("ghx_uexchange_adjoint", "ghx_sexchange_adjoint", "ghx_sexchange_adjoint_self",
-                "ghx_cs_exchange_adjoint", "ghx_cs_exchange_adjoint_self"):
+# the six adjoint families' create, reverse pack and accumulate take the same arguments
+for _prefix in ("ghx_uexchange_adjoint", "ghx_uexchange_adjoint_self", "ghx_sexchange_adjoint",
+                "ghx_sexchange_adjoint_self", "ghx_cs_exchange_adjoint", "ghx_cs_exchange_adjoint_self"):
     _SIGS[_prefix + "_create"] = (c_i32, [c_vp, P(c_i32), c_i32])
     _SIGS[_prefix + "_pack"] = (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_vp])
     _SIGS[_prefix + "_accumulate"] = (c_i32, [c_vp, P(c_vp), c_i32, P(c_vp), c_i32, c_i32, c_vp])

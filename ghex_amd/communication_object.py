@@ -254,7 +254,8 @@ class CommunicationObject:
                  direct: bool = False, epoch_timeout: float = 30.0, fuse_rotated: bool = False,
                  fuse_lists: bool = False, fuse_lists_mixed: bool = False,
                  adjoint_boxes: bool = False, adjoint_rotated: bool = False,
-                 fuse_adjoint: bool = False, fuse_adjoint_rotated: bool = False):
+                 fuse_adjoint: bool = False, fuse_adjoint_rotated: bool = False,
+                 fuse_adjoint_lists: bool = False):
         if staging not in (None, "host"):
             raise ValueError("staging must be None (device buffers) or 'host'")
         if direct and (staging is not None or pipelined or rccl_self):
@@ -308,6 +309,12 @@ class CommunicationObject:
             raise ValueError("fuse_adjoint_rotated fuses the adjoint of cubed-sphere fields: it "
                              "needs adjoint_rotated=True")
         self.fuse_adjoint_rotated = bool(fuse_adjoint_rotated)
+        # the same for unstructured fields: a self message's halo cells are added straight into
+        # their owner cells in the accumulate launch (ghx_uexchange_adjoint_self_*, k_accum_get_u);
+        # the buffers of self messages are not touched. Opt-in; a plan without a self message, or
+        # one the planner refuses (a halo cell of a self message that is an owner cell of another
+        # message), takes the usual path or raises as the create does
+        self.fuse_adjoint_lists = bool(fuse_adjoint_lists)
         self.staging = staging
         self.pipelined = pipelined
         # tests: route the self messages through RCCL too (a 1-rank communicator), so the
@@ -597,7 +604,8 @@ class CommunicationObject:
         regular structured fields ghx_sexchange_adjoint_create, k_accum_s; with adjoint_rotated
         and cubed-sphere fields ghx_cs_exchange_adjoint_create, k_pack_x and k_accum_s; with
         fuse_adjoint_rotated and a self message ghx_cs_exchange_adjoint_self_create,
-        k_accum_get_x)."""
+        k_accum_get_x; with fuse_adjoint_lists, unstructured fields and a self message
+        ghx_uexchange_adjoint_self_create, k_accum_get_u)."""
         if self.direct or self.pipelined:
             raise ValueError("the adjoint exchange is the plain communication object's "
                              "(no direct=True, no pipelined=True)")
@@ -631,6 +639,11 @@ class CommunicationObject:
             if any(x["rank"] == me for x in self.plan(bis).recv):
                 # all self or mixed: the self messages come from the halos (k_accum_get_s)
                 return self._with_adjoint(bis, "ghx_sexchange_adjoint_self_")
+        if not boxes and self.fuse_adjoint_lists and self.fuse_self:
+            me = self.context.rank()
+            if any(x["rank"] == me for x in self.plan(bis).recv):
+                # all self or mixed: the self messages come from the halos (k_accum_get_u)
+                return self._with_adjoint(bis, "ghx_uexchange_adjoint_self_")
         return self._with_adjoint(bis, "ghx_sexchange_adjoint_" if boxes else "ghx_uexchange_adjoint_")
 
     def _with_adjoint(self, bis, prefix):
@@ -656,7 +669,9 @@ class CommunicationObject:
         and the accumulate reads the self messages from the halo cells themselves. The send and
         receive buffers of self messages are then not touched: they keep whatever they held.
         fuse_adjoint_rotated=True (with adjoint_rotated and fuse_self) is the same for
-        cubed-sphere fields: a self message's halo cells are read through the edge's transform."""
+        cubed-sphere fields: a self message's halo cells are read through the edge's transform.
+        fuse_adjoint_lists=True (with fuse_self) is the same for unstructured fields
+        (k_accum_get_u): when every message is a self message the adjoint is one launch."""
         import torch
         bis = self._as_list(buffer_infos)
         stream = torch.cuda.current_stream(bis[0].field.device.index) if bis else None

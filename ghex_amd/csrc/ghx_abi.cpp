@@ -1283,6 +1283,43 @@ int ghx_uaccum_contrib(const ghx_uaccum* p, int64_t j, int32_t* entry, int64_t* 
     });
 }
 
+int ghx_uaccum_get_create(const ghx_upack_entry* contrib, const int32_t* dtypes, const ghx_upack_entry* const* source,
+                          int32_t n, const ghx_upack_entry* zero, int32_t n_zero, ghx_uaccum** out)
+{
+    return guarded([&] {
+        check_ptr(out, "out");
+        *out = nullptr;
+        if (n < 0 || n_zero < 0 || (n && (!contrib || !dtypes)) || (n_zero && !zero)) throw invalid("bad entry arrays");
+        check_ptr(source, "source");
+        *out = new ghx_uaccum(contrib, dtypes, n, zero, n_zero, source);
+        return GHX_OK;
+    });
+}
+
+int ghx_uaccum_get_execute(const ghx_uaccum* p, void* const* field_ptrs, int32_t n_fields,
+                           void* const* buffer_ptrs, int32_t n_buffers, int32_t zero_halos,
+                           ghx_stream stream)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        return p->execute_get(field_ptrs, n_fields, buffer_ptrs, n_buffers, zero_halos != 0, stream);
+    });
+}
+
+int ghx_uaccum_contrib_kind(const ghx_uaccum* p, int64_t j, int32_t* kind, int32_t* slot, int64_t* lid)
+{
+    return guarded([&] {
+        check_ptr(p, "plan");
+        if (j < 0 || uint64_t(j) >= p->contribs.size()) throw invalid("record index out of range");
+        const uint32_t e = p->contribs[size_t(j)].entry;
+        const bool field = p->get && p->get_entries[e].field_src;
+        if (kind) *kind = field ? 1 : 0;
+        if (slot) *slot = field ? int32_t(p->get_entries[e].tab) : int32_t(p->entries[e].buf_slot);
+        if (lid) *lid = field ? p->src_lid[size_t(j)] : -1;
+        return GHX_OK;
+    });
+}
+
 int ghx_uaccum_destroy(ghx_uaccum* p)
 {
     return guarded([&] {
@@ -1291,7 +1328,7 @@ int ghx_uaccum_destroy(ghx_uaccum* p)
     });
 }
 
-// The adjoint of an exchange: five kinds of plan set (exchange_plan::adjoint_kind), one create, one
+// The adjoint of an exchange: six kinds of plan set (exchange_plan::adjoint_kind), one create, one
 // reverse pack and one accumulate behind the entry points of each.
 namespace
 {
@@ -1304,7 +1341,8 @@ const char* const k_no_adjoint[exchange_plan::n_adjoint_kinds] = {
     "adjoint exchange: no adjoint plans (ghx_sexchange_adjoint_create)",
     "fused adjoint exchange: no plans (ghx_sexchange_adjoint_self_create)",
     "cubed-sphere adjoint exchange: no adjoint plans (ghx_cs_exchange_adjoint_create)",
-    "fused cubed-sphere adjoint exchange: no plans (ghx_cs_exchange_adjoint_self_create)"};
+    "fused cubed-sphere adjoint exchange: no plans (ghx_cs_exchange_adjoint_self_create)",
+    "fused adjoint exchange: no plans (ghx_uexchange_adjoint_self_create)"};
 
 const adjoint_set* created_adjoint(const ghx_exchange* ex, adjoint_kind kind)
 {
@@ -1392,6 +1430,41 @@ int ghx_uexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_
 {
     return adjoint_accumulate(ex, exchange_plan::adj_list, field_ptrs, n_fields, send_buffers, n_send, zero_halos,
                               stream);
+}
+
+int ghx_uexchange_adjoint_self_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items)
+{
+    return adjoint_create(ex, exchange_plan::adj_list_self, dtypes, n_items);
+}
+
+int ghx_uexchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64_t* n_dest, int64_t* n_contrib,
+                                    int64_t* n_field_sources)
+{
+    return guarded([&] {
+        check_ptr(ex, "exchange");
+        check_ptr(form, "form");
+        const adjoint_set& set = ex->adjoint[exchange_plan::adj_list_self];
+        const uaccum_plan* p = set.uaccum.get();
+        *form = set.form;
+        if (n_dest) *n_dest = p ? int64_t(p->n_dest) : 0;
+        if (n_contrib) *n_contrib = p ? int64_t(p->contribs.size()) : 0;
+        if (n_field_sources) *n_field_sources = p ? int64_t(p->n_field_sources) : 0;
+        return GHX_OK;
+    });
+}
+
+int ghx_uexchange_adjoint_self_pack(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                    void* const* recv_buffers, int32_t n_recv, ghx_stream stream)
+{
+    return adjoint_pack(ex, exchange_plan::adj_list_self, field_ptrs, n_fields, recv_buffers, n_recv, stream);
+}
+
+int ghx_uexchange_adjoint_self_accumulate(const ghx_exchange* ex, void* const* field_ptrs, int32_t n_fields,
+                                          void* const* send_buffers, int32_t n_send, int32_t zero_halos,
+                                          ghx_stream stream)
+{
+    return adjoint_accumulate(ex, exchange_plan::adj_list_self, field_ptrs, n_fields, send_buffers, n_send,
+                              zero_halos, stream);
 }
 
 int ghx_saccum_create(const ghx_pack_entry* contrib, const int32_t* dtypes, int32_t n,

@@ -1,6 +1,6 @@
-// ghx_accum.hip — gfx950 (CDNA4) adjoint accumulate for index-list halos (k_accum_u) and, further
-// down, for structured fields (k_accum_s, its get form k_accum_get_s and the cubed sphere's
-// k_accum_get_x).
+// ghx_accum.hip — gfx950 (CDNA4) adjoint accumulate for index-list halos (k_accum_u and its get
+// form k_accum_get_u) and, further down, for structured fields (k_accum_s, its get form
+// k_accum_get_s and the cubed sphere's k_accum_get_x).
 //
 // The adjoint of the halo exchange sends every halo copy of a cell back to the cell's owner and
 // sums it there. The contributions are already stored once: they are the message bytes a reverse
@@ -151,6 +151,134 @@ __global__ __launch_bounds__(kBlock) void k_accum_u(kargs_ua a)
         else accum_tile<uint32_t>(a, s);
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// k_accum_get_u: k_accum_u's walk with a record's value taken from a buffer or, a field source,
+// from the halo cell of a receiving field of the same launch (ghx_uaccum_get_create). The planner
+// has resolved the source: the record holds the entry and an index `at` (message position or
+// source lid), the entry the pointer slot and the element strides of `at` and of the level, so
+// both kinds share one address form and the lane's chain stays record -> entry -> value. Wide:
+// the plan's records are acc_get_rec64 (a source lid of 2^31 or more), one table per plan.
+// The planner has verified that one record reads a halo cell and that nothing else touches it, so
+// the lane that loaded it may store zero over it (zero_halos) with no other ordering.
+// ---------------------------------------------------------------------------------------------
+template<typename T, bool Wide>
+__device__ __forceinline__ GHX_GLOBAL T* contrib_addr(const kargs_uag& a, uint32_t j, uint32_t l, uint32_t& field_src)
+{
+    uint32_t entry;
+    uint64_t at;
+    if constexpr (Wide)
+    {
+        const u32x4 c = ((const GHX_GLOBAL u32x4*)a.recs)[j];  // entry, pad, at (2 words)
+        entry = c.x;
+        at = uint64_t(c.z) | (uint64_t(c.w) << 32);
+    }
+    else
+    {
+        const u32x2 c = ((const GHX_GLOBAL u32x2*)a.recs)[j];  // entry, at
+        entry = c.x;
+        at = c.y;
+    }
+    const GHX_GLOBAL u32x4* ep = (const GHX_GLOBAL u32x4*)(a.entries + entry);
+    const u32x4 e0 = ep[0];  // base (2 words), at_stride (2 words)
+    const u32x4 e1 = ep[1];  // lev_stride (2 words), tab, field_src
+    const uint64_t base = uint64_t(e0.x) | (uint64_t(e0.y) << 32);
+    const uint64_t at_stride = uint64_t(e0.z) | (uint64_t(e0.w) << 32);
+    const uint64_t lev_stride = uint64_t(e1.x) | (uint64_t(e1.y) << 32);
+    field_src = e1.w;
+    const uint64_t elem = at * at_stride + uint64_t(l) * lev_stride;  // mod 2^64: strides are signed
+    return (GHX_GLOBAL T*)(reinterpret_cast<char*>(a.ptr[e1.z]) + base + elem * sizeof(T));
+}
+
+template<typename T, bool Wide>
+__device__ __forceinline__ void accum_get_tile(const kargs_uag& a, const acc_tile& s)
+{
+    char* field = reinterpret_cast<char*>(a.ptr[s.field_slot]);
+    const uint32_t ne = s.n_rows * s.levels;  // < 2^32 (planner)
+    for (uint32_t e = threadIdx.x; e < ne; e += kBlock)
+    {
+        uint32_t r, l;
+        tile_element(s, e, r, l);
+        const uint32_t d = s.first_dest + r;
+        const u32x2 rg = ((const GHX_GLOBAL u32x2*)a.ranges)[d];  // first, count
+        const int64_t lid = a.lid64 ? ((const GHX_GLOBAL int64_t*)a.lids)[d] : ((const GHX_GLOBAL int32_t*)a.lids)[d];
+        GHX_GLOBAL T* cell = (GHX_GLOBAL T*)(field + lid * s.index_stride_b + int64_t(l) * s.level_stride_b);
+        T acc = *cell;
+        uint32_t j = rg.x, left = rg.y;
+        if (left == 1)  // a cell with one halo copy, the common one: no clamped loads beside it
+        {
+            uint32_t fs;
+            GHX_GLOBAL T* p = contrib_addr<T, Wide>(a, j, l, fs);
+            const T v = *p;
+            if (a.zero_src & fs) *p = T(0);
+            acc = T(acc + v);
+            left = 0;
+        }
+        while (left)
+        {
+            GHX_GLOBAL T* p[kAccBatch];
+            uint32_t fs[kAccBatch];
+            T v[kAccBatch];
+#pragma unroll
+            for (uint32_t k = 0; k < kAccBatch; ++k)
+            {
+                p[k] = contrib_addr<T, Wide>(a, j + min(k, left - 1), l, fs[k]);
+                v[k] = *p[k];
+            }
+            // zero over the field sources this trip adds; a clamped copy past the end is neither
+#pragma unroll
+            for (uint32_t k = 0; k < kAccBatch; ++k)
+                if (k < left && (a.zero_src & fs[k])) *p[k] = T(0);
+#pragma unroll
+            for (uint32_t k = 0; k < kAccBatch; ++k) acc = k < left ? T(acc + v[k]) : acc;
+            const uint32_t step = min(uint32_t(kAccBatch), left);
+            j += step;
+            left -= step;
+        }
+        *cell = acc;
+    }
+}
+
+template<typename Z>
+__device__ __forceinline__ void zero_get_tile(const kargs_uag& a, const acc_tile& s)
+{
+    char* field = reinterpret_cast<char*>(a.ptr[s.field_slot]);
+    const uint32_t ne = s.n_rows * s.levels;
+    for (uint32_t e = threadIdx.x; e < ne; e += kBlock)
+    {
+        uint32_t r, l;
+        tile_element(s, e, r, l);
+        const uint32_t d = s.first_dest + r;
+        const int64_t lid = a.lid64 ? ((const GHX_GLOBAL int64_t*)a.lids)[d] : ((const GHX_GLOBAL int32_t*)a.lids)[d];
+        *(GHX_GLOBAL Z*)(field + lid * s.index_stride_b + int64_t(l) * s.level_stride_b) = Z(0);
+    }
+}
+
+template<bool Wide>
+__device__ __forceinline__ void accum_get_tiles(const kargs_uag& a)
+{
+    for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x)
+    {
+        const acc_tile s = a.tiles[t];
+        const bool wide = s.dtype == GHX_DT_F64 || s.dtype == GHX_DT_I64;
+        if (s.zero)
+        {
+            if (wide) zero_get_tile<uint64_t>(a, s);
+            else zero_get_tile<uint32_t>(a, s);
+        }
+        else if (s.dtype == GHX_DT_F32) accum_get_tile<float, Wide>(a, s);
+        else if (s.dtype == GHX_DT_F64) accum_get_tile<double, Wide>(a, s);
+        else if (wide) accum_get_tile<uint64_t, Wide>(a, s);
+        else accum_get_tile<uint32_t, Wide>(a, s);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_accum_get_u(kargs_uag a)
+{
+    if (a.rec64) accum_get_tiles<true>(a);
+    else accum_get_tiles<false>(a);
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_accum_s: the adjoint accumulate of structured fields (saccum_plan, ghx_saccum_plan.cpp).
 //
@@ -388,8 +516,9 @@ __global__ __launch_bounds__(kBlock) void k_accum_get_s(kargs_sa a) { accum_tile
 // k_accum_s and k_accum_get_s compile as they did.
 __global__ __launch_bounds__(kBlock) void k_accum_get_x(kargs_sa a) { accum_tiles_s<true, true>(a); }
 
-template<typename K>
-int launch_sa(K kernel, const char* what, const kargs_sa& a, void* stream, uint32_t grid)
+// one launch of an accumulate kernel over the first a.n_tiles tiles (A: the kernel's kargs_*)
+template<typename K, typename A>
+int launch_acc(K kernel, const char* what, const A& a, void* stream, uint32_t grid)
 {
     if (a.n_tiles == 0) return GHX_OK;
     grid = grid < a.n_tiles ? grid : a.n_tiles;
@@ -417,42 +546,27 @@ int launch_sa(K kernel, const char* what, const kargs_sa& a, void* stream, uint3
 
 int launch_accum_get_x(const kargs_sa& a, void* stream, uint32_t grid)
 {
-    return launch_sa(k_accum_get_x, "cubed-sphere adjoint get-accumulate", a, stream, grid);
+    return launch_acc(k_accum_get_x, "cubed-sphere adjoint get-accumulate", a, stream, grid);
 }
 
 int launch_accum_get_s(const kargs_sa& a, void* stream, uint32_t grid)
 {
-    return launch_sa(k_accum_get_s, "structured adjoint get-accumulate", a, stream, grid);
+    return launch_acc(k_accum_get_s, "structured adjoint get-accumulate", a, stream, grid);
 }
 
 int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid)
 {
-    return launch_sa(k_accum_s, "structured adjoint accumulate", a, stream, grid);
+    return launch_acc(k_accum_s, "structured adjoint accumulate", a, stream, grid);
+}
+
+int launch_accum_get_u(const kargs_uag& a, void* stream, uint32_t grid)
+{
+    return launch_acc(k_accum_get_u, "adjoint get-accumulate", a, stream, grid);
 }
 
 int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid)
 {
-    if (a.n_tiles == 0) return GHX_OK;
-    grid = grid < a.n_tiles ? grid : a.n_tiles;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (t_timing && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
-    {
-        hipExtLaunchKernelGGL(k_accum_u, dim3(grid), dim3(kBlock), 0, s, e0, e1, 0, a);
-        t_timing->emplace_back(e0, e1);
-    }
-    else
-    {
-        if (e0) (void)hipEventDestroy(e0);
-        hipLaunchKernelGGL(k_accum_u, dim3(grid), dim3(kBlock), 0, s, a);
-    }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
-    {
-        set_error(std::string("adjoint accumulate kernel launch failed: ") + hipGetErrorString(err));
-        return GHX_ERR_HIP;
-    }
-    return GHX_OK;
+    return launch_acc(k_accum_u, "adjoint accumulate", a, stream, grid);
 }
 
 }  // namespace ghx

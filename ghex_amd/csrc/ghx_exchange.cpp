@@ -816,7 +816,7 @@ using adjoint_kind = exchange_plan::adjoint_kind;
 void check_adjoint_args(const exchange_plan& ex, adjoint_kind kind, const int32_t* dtypes, int32_t n)
 {
     const bool cs = kind == exchange_plan::adj_cs || kind == exchange_plan::adj_cs_self;
-    if (kind == exchange_plan::adj_list)
+    if (kind == exchange_plan::adj_list || kind == exchange_plan::adj_list_self)
     {
         if (!ex.only_unstructured)
             throw invalid("adjoint exchange: the exchange holds a structured or cubed-sphere item (their send "
@@ -870,16 +870,18 @@ struct self_match
 };
 
 // throws unless every entry of a self message has its counterpart and there is a self message;
-// `plain_create` names the create that serves an exchange without one
-self_match match_self_messages(const exchange_plan& ex, const char* plain_create)
+// `plain_create` names the create that serves an exchange without one. se / re: the send and
+// receive entries, of boxes or of lists
+template<typename Entry>
+self_match match_self_messages(const exchange_plan& ex, const std::vector<Entry>& se, const std::vector<Entry>& re,
+                               const char* plain_create)
 {
-    const std::vector<ghx_pack_entry>&se = ex.entries[0], &re = ex.entries[1];
     std::vector<int> recv_of_send(ex.send.size(), -1);
     for (size_t j = 0; j < ex.send_of_recv.size(); ++j)
         if (ex.send_of_recv[j] >= 0) recv_of_send[size_t(ex.send_of_recv[j])] = int(j);
     self_match m;
     std::vector<char> sourced(re.size(), 0);
-    for (const ghx_pack_entry& e : se)
+    for (const Entry& e : se)
     {
         m.recv_of.push_back(-1);
         const int j = recv_of_send[size_t(e.buffer_slot)];
@@ -928,6 +930,30 @@ void exchange_plan::make_adjoint(adjoint_kind kind, const int32_t* dtypes, int32
         adjoint[kind] = std::move(set);
         return;
     }
+    if (kind == adj_list_self)
+    {
+        const std::vector<ghx_upack_entry>&se = uentries[0], &re = uentries[1];
+        const self_match m = match_self_messages(*this, se, re, "ghx_uexchange_adjoint_create");
+        std::vector<int32_t> dt;
+        std::vector<const ghx_upack_entry*> source(se.size(), nullptr);
+        for (size_t e = 0; e < se.size(); ++e)
+        {
+            dt.push_back(dtypes[se[e].field_slot]);
+            if (m.recv_of[e] >= 0) source[e] = &re[size_t(m.recv_of[e])];
+        }
+        set.uaccum = std::make_unique<uaccum_plan>(se.data(), dt.data(), int(dt.size()), re.data(), int(re.size()),
+                                                   source.data());
+        // the reverse pack of the peer receive entries alone
+        if (!m.peer.empty())
+        {
+            std::vector<ghx_upack_entry> peer;
+            for (size_t k : m.peer) peer.push_back(re[k]);
+            set.upack = std::make_unique<uplan>(peer.data(), int(peer.size()), 0);
+        }
+        set.form = m.n_self == se.size() && m.peer.empty() ? 1 : 2;
+        adjoint[kind] = std::move(set);
+        return;
+    }
     const std::vector<ghx_pack_entry>&se = entries[0], &re = entries[1];
     std::vector<int32_t> dt;
     for (const ghx_pack_entry& e : se) dt.push_back(dtypes[e.field_slot]);
@@ -950,7 +976,7 @@ void exchange_plan::make_adjoint(adjoint_kind kind, const int32_t* dtypes, int32
     {
         const bool cs = kind == adj_cs_self;
         const self_match m =
-            match_self_messages(*this, cs ? "ghx_cs_exchange_adjoint_create" : "ghx_sexchange_adjoint_create");
+            match_self_messages(*this, se, re, cs ? "ghx_cs_exchange_adjoint_create" : "ghx_sexchange_adjoint_create");
         std::vector<const ghx_pack_entry*> source(se.size(), nullptr);
         // cubed sphere: the receiving side of each box of a paired entry, box k of one with box k of
         // the other as build_cs_self pairs them
@@ -1021,7 +1047,9 @@ int exchange_plan::adjoint_set::pack(void* const* fptr, int nf, void* const* bpt
 int exchange_plan::adjoint_set::accumulate(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos,
                                            void* stream) const
 {
-    if (uaccum) return uaccum->execute(fptr, nf, bptr, nb, zero_halos, stream);
+    if (uaccum)
+        return uaccum->get ? uaccum->execute_get(fptr, nf, bptr, nb, zero_halos, stream)
+                           : uaccum->execute(fptr, nf, bptr, nb, zero_halos, stream);
     return saccum->get ? saccum->execute_get(fptr, nf, bptr, nb, zero_halos, stream)
                        : saccum->execute(fptr, nf, bptr, nb, zero_halos, stream);
 }

@@ -93,7 +93,10 @@ struct exchange_plan
     //   from the receiving field's halo cells through the edge's transform, and the reverse pack
     //   covers the peer receive spaces alone: the kept ordinary segments and xunpack's boxes filtered
     //   by receive buffer.
-    enum adjoint_kind { adj_list, adj_boxes, adj_boxes_self, adj_cs, adj_cs_self, n_adjoint_kinds };
+    //  list_self (ghx_uexchange_adjoint_self_create): list with the self messages fused. The get plan
+    //   (k_accum_get_u) reads a self message from the receiving field's halo cells, and the reverse
+    //   pack covers the peer receive entries alone.
+    enum adjoint_kind { adj_list, adj_boxes, adj_boxes_self, adj_cs, adj_cs_self, adj_list_self, n_adjoint_kinds };
     struct adjoint_set
     {
         // 0 not created; 1 created (a fused set: every message is a self message); 2 a fused set
@@ -105,8 +108,8 @@ struct exchange_plan
         std::unique_ptr<uplan> upack;
         std::unique_ptr<xplan> own_xpack;
         const xplan* xpack = nullptr;
-        // the accumulate plan: uaccum for list, else saccum (the handle type: the cubed-sphere
-        // *_plan calls lend it); a get plan in the fused sets
+        // the accumulate plan: uaccum for list and list_self, else saccum (the handle type: the
+        // cubed-sphere *_plan calls lend it); a get plan in the fused sets
         std::unique_ptr<uaccum_plan> uaccum;
         std::unique_ptr<::ghx_saccum> saccum;
         // the ordinary launch, then the transformed one on the same stream

@@ -373,6 +373,47 @@ struct kargs_ua
     uint64_t buf_ptr[GHX_MAX_SLOTS];
 };
 
+// The get form (k_accum_get_u, ghx_uaccum_get_create): the destination, range and tile tables of
+// above; what changes is where a record's value is loaded from. A record names its entry and an
+// index `at`: the position in the message for an entry that reads its buffer, the SOURCE LID for
+// an entry that reads the halo cells of a receiving field (resolved by the planner, so a lane's
+// chain is record -> entry -> value for both). Records are acc_get_rec, or acc_get_rec64 when a
+// source lid is 2^31 or more (one table per plan, kargs_uag::rec64). The entry record gives the
+// element strides of `at` and of the level and the pointer the value lies behind: the value of
+// (at, level) is at ptr[tab] + base + (at * at_stride + level * lev_stride) * sizeof(T).
+struct acc_get_rec
+{
+    uint32_t entry, at;
+};
+struct alignas(16) acc_get_rec64
+{
+    uint32_t entry, pad;
+    uint64_t at;
+};
+struct alignas(16) acc_get_entry
+{
+    uint64_t base;        // buffer: the message's byte offset; field source: 0
+    int64_t at_stride;    // in elements. Buffer: 1 or levels; field source: its index stride
+    int64_t lev_stride;   // buffer: n or 1; field source: its level stride
+    uint32_t tab;         // index in kargs_uag::ptr
+    uint32_t field_src;   // 1: a field source, which the loading lane zeroes in a launch with zero_src
+};
+static_assert(sizeof(acc_get_entry) == 32, "acc_get_entry layout");
+struct kargs_uag
+{
+    const acc_tile* tiles;
+    const acc_range* ranges;
+    const void* lids;          // per destination, int32 or int64 (lid64)
+    const void* recs;          // acc_get_rec or acc_get_rec64 (rec64)
+    const acc_get_entry* entries;
+    uint32_t n_tiles;
+    uint32_t lid64;
+    uint32_t rec64;
+    uint32_t zero_src;         // store zero over a field source once it is loaded (zero_halos)
+    // field slot s at [s] (owners and sources alike), buffer slot b at [GHX_MAX_SLOTS + b]
+    uint64_t ptr[2 * GHX_MAX_SLOTS];
+};
+
 // Adjoint accumulate of structured fields (k_accum_s, ghx_accum.hip): the tables
 // of a saccum_plan. The union of a field's contribution boxes is cut into disjoint sub-boxes; every
 // cell of a sub-box has the same sources — the contribution boxes that hold it, in ascending
@@ -488,6 +529,7 @@ int launch_self_u(const kargs& a, void* stream, uint32_t grid, bool runs);
 int launch_pack_self_u(const kargs_um& a, void* stream, uint32_t grid, bool runs);
 // ghx_accum.hip: the adjoint accumulate over the first a.n_tiles tile records
 int launch_accum_u(const kargs_ua& a, void* stream, uint32_t grid);
+int launch_accum_get_u(const kargs_uag& a, void* stream, uint32_t grid);  // k_accum_get_u
 int launch_accum_s(const kargs_sa& a, void* stream, uint32_t grid);
 int launch_accum_get_s(const kargs_sa& a, void* stream, uint32_t grid);  // k_accum_get_s
 int launch_accum_get_x(const kargs_sa& a, void* stream, uint32_t grid);  // k_accum_get_x

@@ -299,9 +299,22 @@ struct uaccum_plan
         tables& operator=(const tables&) = delete;
         ~tables();
     } dev;
+    // A get plan (ghx_uaccum_get_create, k_accum_get_u): `source` names per contribution entry the
+    // halo side of the same message (null: the entry reads its buffer); position i of the entry's
+    // list pairs with position i of the source's. The destinations, ranges, records and sum tiles
+    // are those of the plain plan; src_lid holds per record the source lid (-1: a buffer record)
+    // and get_entries per entry where its values lie. A zero entry that is a contribution's source
+    // (same field slot, same list) gets no zero tile: the accumulate zeroes it as it reads.
+    // rec64: a source lid is 2^31 or more and the device records are acc_get_rec64.
+    bool get = false, rec64 = false;
+    uint64_t n_field_sources = 0;       // contribution entries with a source
+    std::vector<int64_t> src_lid;
+    std::vector<acc_get_entry> get_entries;
     uaccum_plan(const ghx_upack_entry* contrib, const int32_t* dtypes, int n, const ghx_upack_entry* zero,
-                int n_zero);
+                int n_zero, const ghx_upack_entry* const* source = nullptr);
     int execute(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
+    // a get plan's launch (ghx_uaccum_get_execute); each of the two refuses the other kind of plan
+    int execute_get(void* const* fptr, int nf, void* const* bptr, int nb, bool zero_halos, void* stream) const;
 };
 
 // Adjoint accumulate of structured fields (k_accum_s, ghx_saccum_plan.cpp): the

@@ -16,7 +16,10 @@ def make_communication_object(context, fuse_lists: bool = False, **options) -> C
     fuse_lists_mixed (through **options): when an exchange has self AND peer messages, the pack
     launch also writes the self messages' halos and the unpack launch covers the peer messages
     only (ghx_uexchange_pack_self, ghx_uexchange_unpack_peers); an exchange without that form
-    takes the usual path. Both are off by default."""
+    takes the usual path. fuse_adjoint_lists (through **options): adjoint_exchange() adds the halo
+    cells of self messages straight into their owner cells in the accumulate launch
+    (ghx_uexchange_adjoint_self_*, k_accum_get_u) and leaves their buffers alone; an exchange
+    without a self message takes the usual path. All are off by default."""
     return CommunicationObject(context, fuse_lists=fuse_lists, **options)
 
 

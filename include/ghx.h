@@ -955,6 +955,42 @@ int ghx_uaccum_dest(const ghx_uaccum* p, int64_t k, ghx_uaccum_dest_info* out);
 int ghx_uaccum_contrib(const ghx_uaccum* p, int64_t j, int32_t* entry, int64_t* pos);
 int ghx_uaccum_destroy(ghx_uaccum* p);
 
+/* The get-accumulate (k_accum_get_u), the twin of ghx_saccum_get_create: ghx_uaccum_create's
+ * operation, S[s_e[i], l] += R_e[i, l] in ascending (entry, position) per destination cell, where a
+ * contribution entry may read R_e where it lies - the halo cells of a receiving field of the same
+ * launch - instead of a buffer. source[e], e < n, is the halo side of contribution entry e's
+ * message (field slot, descriptor and lids; buffer members ignored; position i pairs with position
+ * i) or NULL: the entry reads its buffer as in ghx_uaccum_create. The array `source` itself is
+ * required, also with n == 0 (a null array is refused). The two sides agree in n_lids,
+ * levels and elem_size and may differ in index_stride, level_stride and levels_first. The
+ * destination table, the ranges, the record order and the sum tiles are those of ghx_uaccum_create
+ * on the same entries, so with the same halo values the sums are the same bit for bit; a record of
+ * an entry with a source holds the source lid, resolved at plan time (records widen to 64-bit
+ * lids, one table per plan, when a source lid is 2^31 or more). zero[k] as in ghx_uaccum_create,
+ * but a zero entry that is a contribution's source (same field slot, same list) gets no zero
+ * tiles: with zero_halos the lane that loaded a halo value stores zero bytes over it. That is
+ * race-free because the planner verifies, and refuses otherwise, that every source cell is read by
+ * one record and touched by nothing else. field_ptrs serve both sides; buffer_ptrs need cover only
+ * the slots of entries without a source (their own buffer members are not looked at otherwise).
+ * ghx_uaccum_info (bytes: the buffer bytes read) / _dest / _contrib / _destroy work on the plan;
+ * ghx_uaccum_execute refuses it, as ghx_uaccum_get_execute refuses a plan of ghx_uaccum_create.
+ * GHX_ERR_INVALID, with the reason, for ghx_uaccum_create's reasons (field slots of sources
+ * included) and when: an entry and its source differ in n_lids, levels or elem_size; a source cell
+ * (field slot, lid) is read by more than one record - a lid repeated within a receive list, or two
+ * receive lists of one field slot naming the same cell; a source cell is also a sum destination;
+ * a source cell lies in a zero entry that is no source. */
+int ghx_uaccum_get_create(const ghx_upack_entry* contrib, const int32_t* dtypes,
+                          const ghx_upack_entry* const* source, int32_t n,
+                          const ghx_upack_entry* zero, int32_t n_zero, ghx_uaccum** out);
+int ghx_uaccum_get_execute(const ghx_uaccum* p, void* const* field_ptrs, int32_t n_fields,
+                           void* const* buffer_ptrs, int32_t n_buffers, int32_t zero_halos,
+                           ghx_stream stream);
+/* Contribution record j (host only, any plan): kind 0 = a buffer, 1 = a field source; the buffer
+ * slot or the source field's slot; the source lid (-1 for a buffer record, whose position
+ * ghx_uaccum_contrib gives). */
+int ghx_uaccum_contrib_kind(const ghx_uaccum* p, int64_t j, int32_t* kind, int32_t* slot,
+                            int64_t* lid);
+
 /* The adjoint of an exchange of unstructured items. ghx_uexchange_adjoint_create builds and
  * attaches two plans (setup time, synchronous upload, as ghx_exchange_split attaches its plans):
  * the reverse pack, a ghx_uplan of direction 0 over the exchange's unpack entries, and the
@@ -976,6 +1012,34 @@ int ghx_uexchange_adjoint_pack(const ghx_exchange* ex, void* const* field_ptrs, 
 int ghx_uexchange_adjoint_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
                                      int32_t n_fields, void* const* send_buffers, int32_t n_send,
                                      int32_t zero_halos, ghx_stream stream);
+
+/* The same adjoint with the self messages fused (k_accum_get_u), the twin of
+ * ghx_sexchange_adjoint_self_*: a message whose receiver is a field of this rank (the pairing of
+ * ghx_uexchange_pack_self: a receive buffer of this rank with a send buffer of the same pair of
+ * domains and size) is accumulated straight from the receiving field's halo cells, and its buffer
+ * is neither written nor read. self_create attaches a get plan (ghx_uaccum_get_create: every send
+ * entry of a self message sourced by the receive entry at the same message bytes) and, where peer
+ * messages remain, a reverse pack over the peer receive entries alone - those
+ * ghx_uexchange_unpack_peers covers. It refuses what ghx_uexchange_adjoint_create refuses, an
+ * exchange with no self message (ghx_uexchange_adjoint_create serves it), a self message whose two
+ * sides do not pair, and ghx_uaccum_get_create's reasons (a halo cell of one self message that is
+ * an owner cell of another message, for one); a refused create leaves every existing plan set as
+ * it was, and the plans of ghx_uexchange_adjoint_create are independent of these. self_info works
+ * on any exchange: form 0 = none, 1 = every message is a self message, 2 = mixed; sum
+ * destinations, contribution records and how many contribution entries have a field source.
+ * self_pack has ghx_uexchange_adjoint_pack's argument contract: form 1 launches nothing and
+ * returns GHX_OK, form 2 gathers the peer messages' halo cells into their receive buffers.
+ * self_accumulate has ghx_uexchange_adjoint_accumulate's: one k_accum_get_u launch, self messages
+ * from the halos, peer messages from the send buffers. */
+int ghx_uexchange_adjoint_self_create(ghx_exchange* ex, const int32_t* dtypes, int32_t n_items);
+int ghx_uexchange_adjoint_self_info(const ghx_exchange* ex, int32_t* form, int64_t* n_dest,
+                                    int64_t* n_contrib, int64_t* n_field_sources);
+int ghx_uexchange_adjoint_self_pack(const ghx_exchange* ex, void* const* field_ptrs,
+                                    int32_t n_fields, void* const* recv_buffers, int32_t n_recv,
+                                    ghx_stream stream);
+int ghx_uexchange_adjoint_self_accumulate(const ghx_exchange* ex, void* const* field_ptrs,
+                                          int32_t n_fields, void* const* send_buffers,
+                                          int32_t n_send, int32_t zero_halos, ghx_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Adjoint halo exchange of structured fields (no reference counterpart): the operation above with
